@@ -13,6 +13,15 @@ work is fixed as N grows.
 Launched by the driver as
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
       --master-addr 127.0.0.1 --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run does only what the headline figure needs: set up, warm up, time
+the K steps, print the one JSON result line. --dump-outputs DIR additionally
+writes what the last timed step returned (the exact tree / solution counts
+and the PFSP optimum) as DIR/<name>.npy, float64 arrays of shape (1,); the
+inputs are fixed by the arguments (N-Queens board size, Taillard generator),
+so with ub=1 two builds must agree value for value. --full is where any
+measurement beyond the headline belongs; there is none today, so it changes
+nothing.
 """
 import argparse
 import json
@@ -44,7 +53,32 @@ def parse_args():
     ap.add_argument("--m", type=int, default=25)
     ap.add_argument("--M", type=int, default=50000)
     ap.add_argument("--mode", default="devpool")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's results as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the measurements beyond the headline (none today)")
     return ap.parse_args()
+
+
+def step_outputs(problem, r):
+    """The values a caller of the timed path receives, by name (wall times
+    and per-run diagnostics excluded: they differ from run to run)."""
+    if problem == "nqueens":
+        return {"tree": r["tree"], "sol": r["sol"]}
+    if problem == "pfsp":
+        return {"tree": r["tree"], "sol": r["sol"], "optimum": r.get("optimum", 0)}
+    return {"nqueens_tree": r["nqueens_tree"], "nqueens_sol": r["nqueens_sol"],
+            "pfsp_tree": r["pfsp_tree"], "pfsp_sol": r["pfsp_sol"],
+            "pfsp_optimum": r["optimum"]}
+
+
+def dump_outputs(path, problem, r):
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    for name, v in step_outputs(problem, r).items():
+        # counts stay far below 2**53, so float64 holds them exactly
+        np.save(os.path.join(path, name + ".npy"), np.array([v], dtype=np.float64))
 
 
 def main():
@@ -81,7 +115,8 @@ def main():
         r2 = gdist.run_pfsp(args.inst, args.lb, args.ub, args.m, args.M, args.mode,
                             engine=engine)
         return {"tree": r1["tree"] + r2["tree"], "nqueens_tree": r1["tree"],
-                "pfsp_tree": r2["tree"], "optimum": r2.get("optimum", 0)}
+                "pfsp_tree": r2["tree"], "optimum": r2.get("optimum", 0),
+                "nqueens_sol": r1["sol"], "pfsp_sol": r2["sol"]}
 
     def sync():
         if world > 1:
@@ -114,6 +149,8 @@ def main():
         elapsed = float(e[0].item())
 
     if rank == 0:
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, args.problem, r)
         total_nodes = nodes_per_step * args.steps
         value = total_nodes / elapsed / 1e6  # Mnodes/s, whole job
         if args.problem == "nqueens":

@@ -7,6 +7,8 @@ import os
 import subprocess
 import sys
 
+import pytest
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 
@@ -32,6 +34,77 @@ def run_bench(nproc, extra):
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout  # exactly ONE JSON line, from rank 0
     return json.loads(lines[0])
+
+
+def run_bench_plain(extra):
+    """bench.py as a plain single process (no torchrun), CPU evaluator."""
+    env = dict(os.environ)
+    env.pop("RANK", None)
+    env.pop("WORLD_SIZE", None)
+    env["GATS_BENCH_CPU"] = "1"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1"] + extra,
+                       capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
+    assert r.returncode == 0, f"stdout:\n{r.stdout}\nstderr:\n{r.stderr}"
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout
+    return json.loads(lines[0])
+
+
+def load_dump(path):
+    import numpy as np
+
+    out = {}
+    for f in sorted(os.listdir(path)):
+        assert f.endswith(".npy"), f
+        a = np.load(os.path.join(path, f))
+        assert a.dtype == np.float64 and a.shape == (1,), (f, a.dtype, a.shape)
+        out[f[:-4]] = float(a[0])
+    return out
+
+
+def test_bench_dump_outputs_nqueens(tmp_path):
+    # --dump-outputs writes what the last timed step returned; --full is
+    # accepted and leaves the result line's contract untouched
+    d = tmp_path / "dump"
+    out = run_bench_plain(["--steps", "2", "--warmup", "1", "--problem", "nqueens",
+                           "--N", "10", "--full", "--dump-outputs", str(d)])
+    assert out["steps"] == 2
+    assert out["metric"] == "Mnodes_per_sec"
+    assert out["dtype"] == "int32"
+    assert out["ms_per_step"] > 0
+    assert load_dump(d) == {"tree": 35538.0, "sol": 724.0}
+
+
+def test_bench_dump_outputs_headline(tmp_path):
+    # headline step: both searches' counts and the proven PFSP optimum
+    # (small stand-ins: N=10 + ta002 lb2, frozen in test_pfsp_seq.py)
+    d = tmp_path / "dump"
+    run_bench_plain(["--steps", "1", "--warmup", "0", "--N", "10",
+                     "--inst", "2", "--lb", "lb2", "--dump-outputs", str(d)])
+    assert load_dump(d) == {"nqueens_tree": 35538.0, "nqueens_sol": 724.0,
+                            "pfsp_tree": 7.0, "pfsp_sol": 0.0, "pfsp_optimum": 1359.0}
+
+
+@pytest.mark.gpu
+def test_bench_dump_outputs_gpu(gpu, tmp_path):
+    # the real timed path (devpool N-Queens + device-rooted PFSP): dumped
+    # counts equal the sequential oracle's (test_nqueens_seq.py N=12,
+    # test_pfsp_seq.py ta014 lb2)
+    d = tmp_path / "dump"
+    env = dict(os.environ)
+    for k in ("RANK", "WORLD_SIZE", "GATS_BENCH_CPU"):
+        env.pop(k, None)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1",
+                        "--steps", "2", "--warmup", "1", "--N", "12", "--inst", "14",
+                        "--lb", "lb2", "--dump-outputs", str(d)],
+                       capture_output=True, text=True, timeout=300, env=env, cwd=ROOT)
+    assert r.returncode == 0, f"stdout:\n{r.stdout}\nstderr:\n{r.stderr}"
+    out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])
+    assert out["steps"] == 2 and out["ms_per_step"] > 0
+    assert out["explored_tree_per_step"] == 856188 + 144639
+    assert load_dump(d) == {"nqueens_tree": 856188.0, "nqueens_sol": 14200.0,
+                            "pfsp_tree": 144639.0, "pfsp_sol": 0.0,
+                            "pfsp_optimum": 1377.0}
 
 
 def test_bench_json_contract_world2():
