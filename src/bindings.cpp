@@ -221,6 +221,60 @@ py::tuple pfsp_seq_step(const py::bytes& nodes, int inst, const std::string& lb_
   return py::make_tuple(tree, sol, best, nodes_to_bytes(pool.data(), pool.size()));
 }
 
+// Single devpool iteration on a chosen pool (kernel-level tests). M defaults
+// to the pool length and capacity to the frontier builders' sizing rule.
+unsigned long long step_arg(const py::object& o, unsigned long long dflt, const char* name) {
+  if (o.is_none()) return dflt;
+  const long long v = o.cast<long long>();
+  if (v < 0) throw std::invalid_argument(std::string(name) + " must be >= 0");
+  return static_cast<unsigned long long>(v);
+}
+
+py::dict step_ctl_to_dict(const DevpoolStepCtl& c) {
+  py::dict d;
+  d["size"] = c.size;
+  d["chunk"] = c.chunk;
+  d["tree"] = c.tree;
+  d["sol"] = c.sol;
+  d["iters"] = c.iters;
+  d["best"] = c.best;
+  d["overflow"] = c.overflow;
+  return d;
+}
+
+py::tuple nq_devpool_step_py(const py::bytes& nodes, int N, int g, int finish, long long m,
+                             const py::object& M, const py::object& capacity,
+                             const std::string& presum, int device) {
+  auto v = nodes_from_bytes<NQNode>(nodes);
+  if (m < 0) throw std::invalid_argument("m must be >= 1");
+  const unsigned long long Mv = step_arg(M, v.empty() ? 1 : v.size(), "M");
+  const unsigned long long cap = step_arg(capacity, v.size() * (MAX_JOBS + 1) + 64, "capacity");
+  DevpoolStepCtl c;
+  {
+    py::gil_scoped_release rel;
+    c = nq_devpool_step(v, N, g, finish, static_cast<unsigned long long>(m), Mv, cap, presum,
+                        device);
+  }
+  return py::make_tuple(nodes_to_bytes(v.data(), v.size()), step_ctl_to_dict(c));
+}
+
+py::tuple pfsp_devpool_step_py(const py::bytes& nodes, int inst, const std::string& lb,
+                               int best, long long m, const py::object& M,
+                               const py::object& capacity, int geom,
+                               const std::string& presum, int device) {
+  auto v = nodes_from_bytes<PFSPNode>(nodes);
+  if (m < 0) throw std::invalid_argument("m must be >= 1");
+  const unsigned long long Mv = step_arg(M, v.empty() ? 1 : v.size(), "M");
+  const unsigned long long cap = step_arg(capacity, v.size() * (MAX_JOBS + 1) + 64, "capacity");
+  DevpoolStepCtl c;
+  {
+    py::gil_scoped_release rel;
+    c = pfsp_devpool_step(v, inst, lb, best, static_cast<unsigned long long>(m), Mv, cap,
+                          geom, presum, device);
+  }
+  return py::make_tuple(nodes_to_bytes(v.data(), v.size()), step_ctl_to_dict(c));
+}
+
 // Exercises pool push/pop/bulk semantics from C++ (unit-test helper).
 py::dict pool_selftest() {
   py::dict d;
@@ -427,6 +481,15 @@ PYBIND11_MODULE(_core, mod) {
           },
           py::arg("inst"), py::arg("lb"), py::arg("nodes"), py::arg("best"),
           py::arg("device") = 0);
+
+  mod.def("nq_devpool_step", &nq_devpool_step_py, py::arg("nodes"), py::arg("N"),
+          py::arg("g") = 1, py::arg("finish") = 8, py::arg("m") = 1,
+          py::arg("M") = py::none(), py::arg("capacity") = py::none(),
+          py::arg("presum") = "auto", py::arg("device") = 0);
+  mod.def("pfsp_devpool_step", &pfsp_devpool_step_py, py::arg("nodes"), py::arg("inst"),
+          py::arg("lb"), py::arg("best"), py::arg("m") = 1, py::arg("M") = py::none(),
+          py::arg("capacity") = py::none(), py::arg("geom") = -1,
+          py::arg("presum") = "auto", py::arg("device") = 0);
 
   mod.def("pool_selftest", &pool_selftest);
   // pure policy helpers (CPU-unit-testable): kernel geometry selection and

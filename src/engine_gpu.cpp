@@ -34,6 +34,7 @@
 #include "engine_gpu.hpp"
 #include "gpu_api.hpp"
 #include "search_host.hpp"
+#include "taillard.hpp"
 
 namespace gats {
 
@@ -394,6 +395,45 @@ int lbk_of(LbKind lb) {
     default:
       return 2;
   }
+}
+
+// Device buffers of one devpool (one slice thread, frontier builder or
+// single-step call). gsum may be a 1-entry dummy when presum is never used.
+template <class NodeT>
+struct DevIterBufs {
+  NodeT* pool;
+  NodeT* childbuf;
+  uint32_t* bc;
+  unsigned long long* bs;
+  unsigned long long* be;  // N-Queens finisher counts; unused for PFSP
+  uint32_t* gsum;
+  int stride;
+  unsigned long long capacity;
+};
+
+// ONE devpool iteration: expand -> (group presum) -> gather2. Every engine
+// loop and the single-step test entry points enqueue exactly this sequence;
+// iteration i reads `cur` and gather2's last block writes `next`. Mi is the
+// chunk window the grids are sized for (callers clamp it to a bound on the
+// live pool size, which leaves the pop rule min(size, M) unchanged).
+void enqueue_nq_iter(const DevIterBufs<NQNode>& b, DevCtl* cur, DevCtl* next, int N, int g,
+                     int finish, unsigned long long m, unsigned long long Mi, bool presum,
+                     hipStream_t s) {
+  const int Gi = devpool_grid(Mi, N, 1);
+  launch_nq_x(cur, b.pool, b.childbuf, b.bc, b.bs, b.be, N, g, finish, m, Mi, s);
+  if (presum) launch_presum(b.bc, b.gsum, Gi, s);
+  launch_gather2_nq(cur, next, b.bc, b.bs, b.be, presum ? b.gsum : nullptr, b.childbuf,
+                    b.pool, b.stride, Gi, m, Mi, b.capacity, s);
+}
+
+void enqueue_pfsp_iter(const DevIterBufs<PFSPNode>& b, DevCtl* cur, DevCtl* next, int jobs,
+                       int machines, int lbg, const PfspDevTables& tb, unsigned long long m,
+                       unsigned long long Mi, bool presum, hipStream_t s) {
+  const int Gi = devpool_grid(Mi, jobs, lbg);
+  launch_pfsp_x(cur, b.pool, b.childbuf, b.bc, b.bs, jobs, machines, lbg, tb, m, Mi, s);
+  if (presum) launch_presum(b.bc, b.gsum, Gi, s);
+  launch_gather2_pfsp(cur, next, b.bc, b.bs, presum ? b.gsum : nullptr, b.childbuf, b.pool,
+                      b.stride, Gi, m, Mi, b.capacity, s);
 }
 
 }  // namespace
@@ -790,20 +830,16 @@ static SliceOut devpool_thread_nq(const std::vector<std::vector<NQNode>>& slices
   const bool presum = G > 1024;
   DevGuard<uint32_t> gsum_d(presum ? (G + 255) / 256 : 1);
   std::vector<NQNode> spilled;  // capacity-pressure spill, re-run after the slice
+  const DevIterBufs<NQNode> bufs{pool_d.p, childbuf_d.p, bc_d.p,  bs_d.p,
+                                 be_d.p,   gsum_d.p,     stride, capacity};
 
   auto iter = [&](int parity, unsigned long long bound) {
     // grid covers only the chunk that can exist (bound >= pool size, so
     // min(size, Mi) == min(size, Mc): the pop rule is unchanged)
     const unsigned long long Mi = std::min(Mc, std::max<unsigned long long>(bound, 1));
-    const int Gi = devpool_grid(Mi, N, 1);
-    const bool ps = presum && Gi > 256;
-    DevCtl* cur = ctl_d.p + parity;
-    DevCtl* next = ctl_d.p + (1 - parity);
-    launch_nq_x(cur, pool_d.p, childbuf_d.p, bc_d.p, bs_d.p, be_d.p, N, g, finish, m, Mi,
-                stream.s);
-    if (ps) launch_presum(bc_d.p, gsum_d.p, Gi, stream.s);
-    launch_gather2_nq(cur, next, bc_d.p, bs_d.p, be_d.p, ps ? gsum_d.p : nullptr,
-                      childbuf_d.p, pool_d.p, stride, Gi, m, Mi, capacity, stream.s);
+    const bool ps = presum && devpool_grid(Mi, N, 1) > 256;
+    enqueue_nq_iter(bufs, ctl_d.p + parity, ctl_d.p + (1 - parity), N, g, finish, m, Mi, ps,
+                    stream.s);
   };
   ReadbackHook hook = [&](DevCtl* hc, DevCtl* live) {
     donate_if_wanted(share, hc, live, pool_d.p, m, stream.s);
@@ -931,18 +967,14 @@ static SliceOut devpool_thread_pfsp(const std::vector<std::vector<PFSPNode>>& sl
   DevGuard<uint32_t> gsum_d(presum ? (G + 255) / 256 : 1);
 
   std::vector<PFSPNode> spilled;  // capacity-pressure spill, re-run after the slice
+  const DevIterBufs<PFSPNode> bufs{pool_d.p, childbuf_d.p, bc_d.p,  bs_d.p,
+                                   nullptr,  gsum_d.p,     stride, capacity};
 
   auto iter = [&](int parity, unsigned long long bound) {
     const unsigned long long Mi = std::min(Mc, std::max<unsigned long long>(bound, 1));
-    const int Gi = devpool_grid(Mi, jobs, lbg);
-    const bool ps = presum && (lbg == 2 || Gi > 256);
-    DevCtl* cur = ctl_d.p + parity;
-    DevCtl* next = ctl_d.p + (1 - parity);
-    launch_pfsp_x(cur, pool_d.p, childbuf_d.p, bc_d.p, bs_d.p, jobs, machines, lbg,
-                  tb, m, Mi, stream.s);
-    if (ps) launch_presum(bc_d.p, gsum_d.p, Gi, stream.s);
-    launch_gather2_pfsp(cur, next, bc_d.p, bs_d.p, ps ? gsum_d.p : nullptr,
-                        childbuf_d.p, pool_d.p, stride, Gi, m, Mi, capacity, stream.s);
+    const bool ps = presum && (lbg == 2 || devpool_grid(Mi, jobs, lbg) > 256);
+    enqueue_pfsp_iter(bufs, ctl_d.p + parity, ctl_d.p + (1 - parity), jobs, machines, lbg, tb,
+                      m, Mi, ps, stream.s);
   };
   ReadbackHook hook = [&](DevCtl* hc, DevCtl* live) {
     donate_if_wanted(share, hc, live, pool_d.p, m, stream.s);
@@ -1495,6 +1527,8 @@ std::vector<NQNode> nq_gpu_frontier(int N, int g, size_t target, int device,
   int finish = 8;
   if (const char* e = std::getenv("GATS_NQ_FINISH")) finish = atoi(e);
   if (finish > 8) finish = 8;
+  const DevIterBufs<NQNode> bufs{pool_d.p, childbuf_d.p, bc_d.p, bs_d.p,
+                                 be_d.p,   nullptr,      stride, capacity};
 
   NQNode root = nq_root();
   DevCtl ctl{};
@@ -1507,13 +1541,8 @@ std::vector<NQNode> nq_gpu_frontier(int N, int g, size_t target, int device,
   auto iter = [&](int parity, unsigned long long bound) {
     const unsigned long long Mi =
         std::min<unsigned long long>(M, std::max<unsigned long long>(bound, 1));
-    const int Gi = devpool_grid(Mi, N, 1);
-    DevCtl* cur = ctl_d.p + parity;
-    DevCtl* next = ctl_d.p + (1 - parity);
-    launch_nq_x(cur, pool_d.p, childbuf_d.p, bc_d.p, bs_d.p, be_d.p, N, g, finish, 1, Mi,
-                stream.s);
-    launch_gather2_nq(cur, next, bc_d.p, bs_d.p, be_d.p, nullptr, childbuf_d.p, pool_d.p,
-                      stride, Gi, 1, Mi, capacity, stream.s);
+    enqueue_nq_iter(bufs, ctl_d.p + parity, ctl_d.p + (1 - parity), N, g, finish, 1, Mi,
+                    /*presum=*/false, stream.s);
   };
   DevLoopCfg cfg;
   cfg.m = 1;
@@ -1557,6 +1586,8 @@ std::vector<PFSPNode> pfsp_gpu_frontier(const PfspInstance& I, int lbk, size_t t
   DevGuard<unsigned long long> bs_d(G);
   const bool presum = (lbg == 2);
   DevGuard<uint32_t> gsum_d(presum ? (G + 255) / 256 : 1);
+  const DevIterBufs<PFSPNode> bufs{pool_d.p, childbuf_d.p, bc_d.p,  bs_d.p,
+                                   nullptr,  gsum_d.p,     stride, capacity};
 
   PFSPNode root = pfsp_root();
   DevCtl ctl{};
@@ -1571,15 +1602,8 @@ std::vector<PFSPNode> pfsp_gpu_frontier(const PfspInstance& I, int lbk, size_t t
   auto iter = [&](int parity, unsigned long long bound) {
     const unsigned long long Mi =
         std::min<unsigned long long>(M, std::max<unsigned long long>(bound, 1));
-    const int Gi = devpool_grid(Mi, jobs, lbg);
-    const bool ps = presum && (lbg == 2 || Gi > 256);
-    DevCtl* cur = ctl_d.p + parity;
-    DevCtl* next = ctl_d.p + (1 - parity);
-    launch_pfsp_x(cur, pool_d.p, childbuf_d.p, bc_d.p, bs_d.p, jobs, machines, lbg, tb, 1,
-                  Mi, stream.s);
-    if (ps) launch_presum(bc_d.p, gsum_d.p, Gi, stream.s);
-    launch_gather2_pfsp(cur, next, bc_d.p, bs_d.p, ps ? gsum_d.p : nullptr,
-                        childbuf_d.p, pool_d.p, stride, Gi, 1, Mi, capacity, stream.s);
+    enqueue_pfsp_iter(bufs, ctl_d.p + parity, ctl_d.p + (1 - parity), jobs, machines, lbg, tb,
+                      1, Mi, presum, stream.s);
   };
   DevLoopCfg cfg;
   cfg.m = 1;
@@ -1600,6 +1624,178 @@ std::vector<PFSPNode> pfsp_gpu_frontier(const PfspInstance& I, int lbk, size_t t
     std::memcpy(nodes.data(), stage.p, fin.size * sizeof(PFSPNode));
   }
   return nodes;
+}
+
+// ---------------------------------------------------------------------------
+// Single-iteration entry points (declared in engine_gpu.hpp): upload a chosen
+// pool, run exactly ONE devpool iteration through enqueue_*_iter, read the
+// pool and the next control block back. The step tests compare every byte
+// and counter with a CPU oracle.
+// ---------------------------------------------------------------------------
+
+namespace {
+
+int presum_mode(const std::string& presum) {
+  if (presum == "auto") return -1;
+  if (presum == "on") return 1;
+  if (presum == "off") return 0;
+  throw std::invalid_argument("presum must be 'auto', 'on' or 'off'");
+}
+
+void validate_step_window(size_t n, int per, unsigned long long m, unsigned long long M,
+                          unsigned long long capacity) {
+  if (m < 1) throw std::invalid_argument("m must be >= 1");
+  if (M < 1) throw std::invalid_argument("M must be >= 1");
+  if (M > (1ull << 31) / static_cast<unsigned long long>(per))
+    throw std::invalid_argument("M * branching must be <= 2^31");
+  if (capacity < n) throw std::invalid_argument("capacity must be >= the number of nodes");
+}
+
+template <class NodeT>
+DevpoolStepCtl step_readback(std::vector<NodeT>& nodes, const NodeT* pool_d,
+                             const DevCtl* ctl_next_d, unsigned long long capacity,
+                             hipStream_t s) {
+  DevCtl fin{};
+  HIP_CHECK(hipMemcpyAsync(&fin, ctl_next_d, sizeof(DevCtl), hipMemcpyDeviceToHost, s));
+  HIP_CHECK(hipStreamSynchronize(s));
+  if (fin.size > capacity) throw std::runtime_error("devpool step: size exceeds capacity");
+  nodes.resize(fin.size);
+  if (fin.size > 0) {
+    HIP_CHECK(hipMemcpyAsync(nodes.data(), pool_d, fin.size * sizeof(NodeT),
+                             hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+  }
+  return {fin.size, fin.chunk, fin.tree, fin.sol, fin.iters, fin.best, fin.overflow};
+}
+
+}  // namespace
+
+void validate_nq_step(const std::vector<NQNode>& nodes, int N, int g, int finish,
+                      unsigned long long m, unsigned long long M,
+                      unsigned long long capacity, const std::string& presum) {
+  // the expand kernel stages EMIT_TILE / 4 + 2 parents per block: N >= 4
+  if (N < 4 || N > MAX_JOBS) throw std::invalid_argument("N must be in 4..20");
+  if (g < 1) throw std::invalid_argument("g must be >= 1");
+  if (finish < -1 || finish > 8) throw std::invalid_argument("finish must be in -1..8");
+  validate_step_window(nodes.size(), N, m, M, capacity);
+  presum_mode(presum);
+  for (size_t i = 0; i < nodes.size(); i++) {
+    const NQNode& p = nodes[i];
+    if (p.depth > N)
+      throw std::invalid_argument("node " + std::to_string(i) + ": depth > N");
+    uint32_t seen = 0;
+    for (int j = 0; j < N; j++) {
+      if (p.board[j] >= N || (seen >> p.board[j] & 1u))
+        throw std::invalid_argument("node " + std::to_string(i) +
+                                    ": board[0:N] is not a permutation of 0..N-1");
+      seen |= 1u << p.board[j];
+    }
+  }
+}
+
+void validate_pfsp_step(const std::vector<PFSPNode>& nodes, int inst, const std::string& lb,
+                        unsigned long long m, unsigned long long M,
+                        unsigned long long capacity, int geom, const std::string& presum) {
+  const LbKind lbk = lb_from_string(lb);
+  const int jobs = taillard_nb_jobs(inst);
+  if (jobs > MAX_JOBS)
+    throw std::invalid_argument("instance exceeds MAX_JOBS=20 (use ta001..ta030)");
+  if (geom != -1 && geom != 2 && geom != 3)
+    throw std::invalid_argument("geom must be -1, 2 or 3");
+  if (geom != -1 && lbk != LbKind::LB2)
+    throw std::invalid_argument("geom 2/3 select an lb2 kernel: lb must be 'lb2'");
+  validate_step_window(nodes.size(), jobs, m, M, capacity);
+  presum_mode(presum);
+  for (size_t i = 0; i < nodes.size(); i++) {
+    const PFSPNode& p = nodes[i];
+    if (p.depth < 0 || p.depth > jobs - 1)
+      throw std::invalid_argument("node " + std::to_string(i) + ": depth not in 0..jobs-1");
+    if (p.limit1 != p.depth - 1)
+      throw std::invalid_argument("node " + std::to_string(i) + ": limit1 != depth - 1");
+    uint32_t seen = 0;
+    for (int j = 0; j < jobs; j++) {
+      if (p.prmu[j] >= jobs || (seen >> p.prmu[j] & 1u))
+        throw std::invalid_argument("node " + std::to_string(i) +
+                                    ": prmu[0:jobs] is not a permutation of 0..jobs-1");
+      seen |= 1u << p.prmu[j];
+    }
+  }
+}
+
+DevpoolStepCtl nq_devpool_step(std::vector<NQNode>& nodes, int N, int g, int finish,
+                               unsigned long long m, unsigned long long M,
+                               unsigned long long capacity, const std::string& presum,
+                               int device) {
+  validate_nq_step(nodes, N, g, finish, m, M, capacity, presum);  // before any HIP call
+  const int pm = presum_mode(presum);
+  const size_t n = nodes.size();
+  // grids sized to the pool that exists, like the engine loops' chunk bound
+  // (bound >= size, so min(size, Mi) == min(size, M))
+  const unsigned long long Mi = std::min<unsigned long long>(M, std::max<size_t>(n, 1));
+  set_device_cached(device);
+  StreamGuard stream;
+  DevGuard<NQNode> pool_d(std::max<unsigned long long>(capacity, 1));
+  DevGuard<DevCtl> ctl_d(2);
+  const int G = devpool_grid(Mi, N, 1);
+  const int stride = devpool_stride(1);
+  DevGuard<NQNode> childbuf_d(static_cast<size_t>(G) * stride);
+  DevGuard<uint32_t> bc_d(G);
+  DevGuard<unsigned long long> bs_d(G), be_d(G);
+  DevGuard<uint32_t> gsum_d((G + 255) / 256);
+  const bool ps = pm < 0 ? G > 1024 : pm == 1;  // auto: devpool_thread_nq's rule
+  const DevIterBufs<NQNode> bufs{pool_d.p, childbuf_d.p, bc_d.p,  bs_d.p,
+                                 be_d.p,   gsum_d.p,     stride, capacity};
+  DevCtl ctl{};
+  ctl.size = n;
+  if (n > 0)
+    HIP_CHECK(hipMemcpyAsync(pool_d.p, nodes.data(), n * sizeof(NQNode),
+                             hipMemcpyHostToDevice, stream.s));
+  HIP_CHECK(hipMemcpyAsync(ctl_d.p, &ctl, sizeof(DevCtl), hipMemcpyHostToDevice, stream.s));
+  HIP_CHECK(hipMemcpyAsync(ctl_d.p + 1, &ctl, sizeof(DevCtl), hipMemcpyHostToDevice, stream.s));
+  HIP_CHECK(hipStreamSynchronize(stream.s));
+  enqueue_nq_iter(bufs, ctl_d.p, ctl_d.p + 1, N, g, finish, m, Mi, ps, stream.s);
+  HIP_CHECK(hipGetLastError());
+  return step_readback(nodes, pool_d.p, ctl_d.p + 1, capacity, stream.s);
+}
+
+DevpoolStepCtl pfsp_devpool_step(std::vector<PFSPNode>& nodes, int inst, const std::string& lb,
+                                 int best, unsigned long long m, unsigned long long M,
+                                 unsigned long long capacity, int geom,
+                                 const std::string& presum, int device) {
+  validate_pfsp_step(nodes, inst, lb, m, M, capacity, geom, presum);  // before any HIP call
+  const int pm = presum_mode(presum);
+  const PfspInstance& I = pfsp_instance_cached(inst, 1);
+  const int jobs = I.jobs, machines = I.machines;
+  const int lbg = geom < 0 ? devpool_lbk_geom(lbk_of(lb_from_string(lb)), machines) : geom;
+  const size_t n = nodes.size();
+  const unsigned long long Mi = std::min<unsigned long long>(M, std::max<size_t>(n, 1));
+  set_device_cached(device);
+  const PfspDevTables& tb = pfsp_tables_cached(I, device);
+  StreamGuard stream;
+  DevGuard<PFSPNode> pool_d(std::max<unsigned long long>(capacity, 1));
+  DevGuard<DevCtl> ctl_d(2);
+  const int G = devpool_grid(Mi, jobs, lbg);
+  const int stride = devpool_stride(lbg);
+  DevGuard<PFSPNode> childbuf_d(static_cast<size_t>(G) * stride);
+  DevGuard<uint32_t> bc_d(G);
+  DevGuard<unsigned long long> bs_d(G);
+  DevGuard<uint32_t> gsum_d((G + 255) / 256);
+  // auto: devpool_thread_pfsp's rule (pfsp_gpu_frontier's is its lbg == 2 half)
+  const bool ps = pm < 0 ? (lbg == 2 || G > 1024) : pm == 1;
+  const DevIterBufs<PFSPNode> bufs{pool_d.p, childbuf_d.p, bc_d.p,  bs_d.p,
+                                   nullptr,  gsum_d.p,     stride, capacity};
+  DevCtl ctl{};
+  ctl.size = n;
+  ctl.best = best;
+  if (n > 0)
+    HIP_CHECK(hipMemcpyAsync(pool_d.p, nodes.data(), n * sizeof(PFSPNode),
+                             hipMemcpyHostToDevice, stream.s));
+  HIP_CHECK(hipMemcpyAsync(ctl_d.p, &ctl, sizeof(DevCtl), hipMemcpyHostToDevice, stream.s));
+  HIP_CHECK(hipMemcpyAsync(ctl_d.p + 1, &ctl, sizeof(DevCtl), hipMemcpyHostToDevice, stream.s));
+  HIP_CHECK(hipStreamSynchronize(stream.s));
+  enqueue_pfsp_iter(bufs, ctl_d.p, ctl_d.p + 1, jobs, machines, lbg, tb, m, Mi, ps, stream.s);
+  HIP_CHECK(hipGetLastError());
+  return step_readback(nodes, pool_d.p, ctl_d.p + 1, capacity, stream.s);
 }
 
 // ---------------------------------------------------------------------------

@@ -173,6 +173,35 @@ std::vector<PFSPNode> pfsp_gpu_frontier(const PfspInstance& I, int lbk, size_t t
                                         int device, int best0, uint64_t& tree,
                                         uint64_t& sol, int& best_out);
 
+// Single-iteration entry points (kernel-level tests): upload `nodes` as the
+// pool, set both parity control blocks to size = nodes.size() (and `best`),
+// run exactly ONE devpool iteration (expand, optional presum, gather2) with
+// the engines' launch helper, and read back the next control block plus the
+// first `size` pool nodes (into `nodes`). `presum` is "auto" (the engines'
+// rule), "on" or "off" (groupSums pointer forced present / null). For PFSP,
+// geom -1 = devpool_lbk_geom's choice, 2 / 3 force the wave-cooperative /
+// per-lane lb2 kernel on any machine count. Inputs are validated on the host
+// BEFORE the first HIP call (std::invalid_argument), so arbitrary bytes can
+// never reach a kernel; the validate_* functions are the same checks alone.
+struct DevpoolStepCtl {
+  unsigned long long size, chunk, tree, sol, iters;
+  int best, overflow;
+};
+void validate_nq_step(const std::vector<NQNode>& nodes, int N, int g, int finish,
+                      unsigned long long m, unsigned long long M,
+                      unsigned long long capacity, const std::string& presum);
+void validate_pfsp_step(const std::vector<PFSPNode>& nodes, int inst, const std::string& lb,
+                        unsigned long long m, unsigned long long M,
+                        unsigned long long capacity, int geom, const std::string& presum);
+DevpoolStepCtl nq_devpool_step(std::vector<NQNode>& nodes, int N, int g, int finish,
+                               unsigned long long m, unsigned long long M,
+                               unsigned long long capacity, const std::string& presum,
+                               int device);
+DevpoolStepCtl pfsp_devpool_step(std::vector<PFSPNode>& nodes, int inst, const std::string& lb,
+                                 int best, unsigned long long m, unsigned long long M,
+                                 unsigned long long capacity, int geom,
+                                 const std::string& presum, int device);
+
 std::vector<uint8_t> nq_gpu_labels(int N, int g, const std::vector<NQNode>& nodes,
                                    int device);
 std::vector<int32_t> pfsp_gpu_bounds(int inst, const std::string& lb,

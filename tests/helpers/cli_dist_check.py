@@ -11,7 +11,11 @@ from gats_amd import cli  # noqa: E402
 def main():
     cli.main(["nqueens", "--N", "10", "--tier", "dist"])
     cli.main(["pfsp", "--inst", "14", "--lb", "lb1_d", "--ub", "1", "--tier", "dist"])
-    print("CLI_DIST_OK")
+    # rank 0 alone owns stdout (it prints the result blocks): a marker from
+    # another rank can land in the middle of one of its lines. The other
+    # ranks' completion is covered by torchrun's exit status.
+    if int(os.environ.get("RANK", "0")) == 0:
+        print("CLI_DIST_OK", flush=True)
 
 
 if __name__ == "__main__":
