@@ -275,6 +275,59 @@ py::tuple pfsp_devpool_step_py(const py::bytes& nodes, int inst, const std::stri
   return py::make_tuple(nodes_to_bytes(v.data(), v.size()), step_ctl_to_dict(c));
 }
 
+// k devpool iterations over one set of buffers (kernel-level tests): a list of
+// (pool bytes, ctl dict) snapshots, one per iteration.
+std::vector<unsigned long long> chain_windows(const std::vector<long long>& windows) {
+  std::vector<unsigned long long> w;
+  for (long long v : windows) {
+    if (v < 1) throw std::invalid_argument("every window must be >= 1");
+    w.push_back(static_cast<unsigned long long>(v));
+  }
+  return w;
+}
+
+template <class NodeT>
+py::list chain_to_list(const std::vector<DevpoolSnapshot<NodeT>>& snaps) {
+  py::list out;
+  for (const auto& s : snaps)
+    out.append(py::make_tuple(nodes_to_bytes(s.nodes.data(), s.nodes.size()),
+                              step_ctl_to_dict(s.ctl)));
+  return out;
+}
+
+py::list nq_devpool_chain_py(const py::bytes& nodes, int N, const std::vector<long long>& windows,
+                             int g, int finish, long long m, const py::object& capacity,
+                             const std::string& presum, int device) {
+  auto v = nodes_from_bytes<NQNode>(nodes);
+  if (m < 0) throw std::invalid_argument("m must be >= 1");
+  const auto w = chain_windows(windows);
+  const unsigned long long cap = step_arg(capacity, v.size() * (MAX_JOBS + 1) + 64, "capacity");
+  std::vector<DevpoolSnapshot<NQNode>> snaps;
+  {
+    py::gil_scoped_release rel;
+    snaps = nq_devpool_chain(v, N, g, finish, static_cast<unsigned long long>(m), w, cap,
+                             presum, device);
+  }
+  return chain_to_list(snaps);
+}
+
+py::list pfsp_devpool_chain_py(const py::bytes& nodes, int inst, const std::string& lb,
+                               int best, const std::vector<long long>& windows, long long m,
+                               const py::object& capacity, int geom, const std::string& presum,
+                               int device) {
+  auto v = nodes_from_bytes<PFSPNode>(nodes);
+  if (m < 0) throw std::invalid_argument("m must be >= 1");
+  const auto w = chain_windows(windows);
+  const unsigned long long cap = step_arg(capacity, v.size() * (MAX_JOBS + 1) + 64, "capacity");
+  std::vector<DevpoolSnapshot<PFSPNode>> snaps;
+  {
+    py::gil_scoped_release rel;
+    snaps = pfsp_devpool_chain(v, inst, lb, best, static_cast<unsigned long long>(m), w, cap,
+                               geom, presum, device);
+  }
+  return chain_to_list(snaps);
+}
+
 // Exercises pool push/pop/bulk semantics from C++ (unit-test helper).
 py::dict pool_selftest() {
   py::dict d;
@@ -488,6 +541,14 @@ PYBIND11_MODULE(_core, mod) {
           py::arg("presum") = "auto", py::arg("device") = 0);
   mod.def("pfsp_devpool_step", &pfsp_devpool_step_py, py::arg("nodes"), py::arg("inst"),
           py::arg("lb"), py::arg("best"), py::arg("m") = 1, py::arg("M") = py::none(),
+          py::arg("capacity") = py::none(), py::arg("geom") = -1,
+          py::arg("presum") = "auto", py::arg("device") = 0);
+  mod.def("nq_devpool_chain", &nq_devpool_chain_py, py::arg("nodes"), py::arg("N"),
+          py::arg("windows"), py::arg("g") = 1, py::arg("finish") = 8, py::arg("m") = 1,
+          py::arg("capacity") = py::none(), py::arg("presum") = "auto",
+          py::arg("device") = 0);
+  mod.def("pfsp_devpool_chain", &pfsp_devpool_chain_py, py::arg("nodes"), py::arg("inst"),
+          py::arg("lb"), py::arg("best"), py::arg("windows"), py::arg("m") = 1,
           py::arg("capacity") = py::none(), py::arg("geom") = -1,
           py::arg("presum") = "auto", py::arg("device") = 0);
 

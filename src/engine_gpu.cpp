@@ -436,6 +436,26 @@ void enqueue_pfsp_iter(const DevIterBufs<PFSPNode>& b, DevCtl* cur, DevCtl* next
                       b.stride, Gi, m, Mi, b.capacity, s);
 }
 
+// Per-iteration launch policy of the devpool engine threads (and of the chain
+// test entry points, so that they launch what the engines launch): the grid
+// window Mi covers only the chunk that can exist (bound >= pool size, so
+// min(size, Mi) == min(size, Mc): the pop rule is unchanged), and the group
+// presum runs only where the buffers were sized for it (presum_alloc) and the
+// prefix walk is long enough to pay for the extra launch.
+struct DevIterPolicy {
+  unsigned long long Mi;
+  bool ps;
+};
+
+bool devpool_presum_alloc(int G, int lbg) { return lbg == 2 || G > 1024; }
+
+DevIterPolicy devpool_iter_policy(unsigned long long Mc, unsigned long long bound, int per,
+                                  int lbg, bool presum_alloc) {
+  const unsigned long long Mi = std::min(Mc, std::max<unsigned long long>(bound, 1));
+  const bool ps = presum_alloc && (lbg == 2 || devpool_grid(Mi, per, lbg) > 256);
+  return {Mi, ps};
+}
+
 }  // namespace
 
 
@@ -827,19 +847,16 @@ static SliceOut devpool_thread_nq(const std::vector<std::vector<NQNode>>& slices
   DevGuard<unsigned long long> bs_d(G), be_d(G);
   // group sums keep gather's prefix walk O(G/256): at the wide chunk G is
   // ~8700 blocks and the linear walk dominated gather (193 us avg at N=17)
-  const bool presum = G > 1024;
+  const bool presum = devpool_presum_alloc(G, 1);
   DevGuard<uint32_t> gsum_d(presum ? (G + 255) / 256 : 1);
   std::vector<NQNode> spilled;  // capacity-pressure spill, re-run after the slice
   const DevIterBufs<NQNode> bufs{pool_d.p, childbuf_d.p, bc_d.p,  bs_d.p,
                                  be_d.p,   gsum_d.p,     stride, capacity};
 
   auto iter = [&](int parity, unsigned long long bound) {
-    // grid covers only the chunk that can exist (bound >= pool size, so
-    // min(size, Mi) == min(size, Mc): the pop rule is unchanged)
-    const unsigned long long Mi = std::min(Mc, std::max<unsigned long long>(bound, 1));
-    const bool ps = presum && devpool_grid(Mi, N, 1) > 256;
-    enqueue_nq_iter(bufs, ctl_d.p + parity, ctl_d.p + (1 - parity), N, g, finish, m, Mi, ps,
-                    stream.s);
+    const DevIterPolicy it = devpool_iter_policy(Mc, bound, N, 1, presum);
+    enqueue_nq_iter(bufs, ctl_d.p + parity, ctl_d.p + (1 - parity), N, g, finish, m, it.Mi,
+                    it.ps, stream.s);
   };
   ReadbackHook hook = [&](DevCtl* hc, DevCtl* live) {
     donate_if_wanted(share, hc, live, pool_d.p, m, stream.s);
@@ -963,7 +980,7 @@ static SliceOut devpool_thread_pfsp(const std::vector<std::vector<PFSPNode>>& sl
   DevGuard<unsigned long long> bs_d(G);
   // group sums keep gather's prefix walk O(G/256) (always needed for lb2's
   // per-wave counts; needed for thread-per-child paths once the chunk is wide)
-  const bool presum = (lbg == 2) || G > 1024;
+  const bool presum = devpool_presum_alloc(G, lbg);
   DevGuard<uint32_t> gsum_d(presum ? (G + 255) / 256 : 1);
 
   std::vector<PFSPNode> spilled;  // capacity-pressure spill, re-run after the slice
@@ -971,10 +988,9 @@ static SliceOut devpool_thread_pfsp(const std::vector<std::vector<PFSPNode>>& sl
                                    nullptr,  gsum_d.p,     stride, capacity};
 
   auto iter = [&](int parity, unsigned long long bound) {
-    const unsigned long long Mi = std::min(Mc, std::max<unsigned long long>(bound, 1));
-    const bool ps = presum && (lbg == 2 || devpool_grid(Mi, jobs, lbg) > 256);
+    const DevIterPolicy it = devpool_iter_policy(Mc, bound, jobs, lbg, presum);
     enqueue_pfsp_iter(bufs, ctl_d.p + parity, ctl_d.p + (1 - parity), jobs, machines, lbg, tb,
-                      m, Mi, ps, stream.s);
+                      m, it.Mi, it.ps, stream.s);
   };
   ReadbackHook hook = [&](DevCtl* hc, DevCtl* live) {
     donate_if_wanted(share, hc, live, pool_d.p, m, stream.s);
@@ -1796,6 +1812,169 @@ DevpoolStepCtl pfsp_devpool_step(std::vector<PFSPNode>& nodes, int inst, const s
   enqueue_pfsp_iter(bufs, ctl_d.p, ctl_d.p + 1, jobs, machines, lbg, tb, m, Mi, ps, stream.s);
   HIP_CHECK(hipGetLastError());
   return step_readback(nodes, pool_d.p, ctl_d.p + 1, capacity, stream.s);
+}
+
+// ---------------------------------------------------------------------------
+// Chain entry points (declared in engine_gpu.hpp): k iterations back to back
+// over ONE set of buffers sized for the largest window, alternating control
+// blocks, no host synchronisation in between — the launch shape of the engine
+// threads, minus the loop driver. A snapshot of the live control block and of
+// the pool follows every iteration on the same stream.
+// ---------------------------------------------------------------------------
+
+namespace {
+
+constexpr unsigned long long CHAIN_MAX_ITERS = 16;
+constexpr unsigned long long CHAIN_MAX_NODES = 1ull << 22;  // capacity * (k + 1)
+
+void validate_chain_windows(const std::vector<unsigned long long>& windows, int per,
+                            unsigned long long capacity) {
+  const unsigned long long k = windows.size();
+  if (k < 1 || k > CHAIN_MAX_ITERS)
+    throw std::invalid_argument("windows must hold 1..16 entries");
+  for (unsigned long long w : windows) {
+    if (w < 1) throw std::invalid_argument("every window must be >= 1");
+    if (w > (1ull << 31) / static_cast<unsigned long long>(per))
+      throw std::invalid_argument("window * branching must be <= 2^31");
+  }
+  if (capacity > CHAIN_MAX_NODES / (k + 1))
+    throw std::invalid_argument("capacity * (len(windows) + 1) must be <= 2^22 nodes");
+}
+
+// Snapshot areas + the read-back shared by both problems. `enqueue(i, cur,
+// next)` enqueues iteration i.
+template <class NodeT, class Enqueue>
+std::vector<DevpoolSnapshot<NodeT>> run_chain(const std::vector<NodeT>& nodes, NodeT* pool_d,
+                                              DevCtl* ctl_d, int best,
+                                              const std::vector<unsigned long long>& windows,
+                                              unsigned long long m,
+                                              unsigned long long capacity, hipStream_t s,
+                                              Enqueue enqueue) {
+  const size_t n = nodes.size();
+  const size_t k = windows.size();
+  DevGuard<NodeT> snap_pool_d(std::max<size_t>(capacity * k, 1));
+  DevGuard<DevCtl> snap_ctl_d(k);
+  DevCtl ctl{};
+  ctl.size = n;
+  ctl.best = best;
+  if (n > 0)
+    HIP_CHECK(hipMemcpyAsync(pool_d, nodes.data(), n * sizeof(NodeT), hipMemcpyHostToDevice, s));
+  HIP_CHECK(hipMemcpyAsync(ctl_d, &ctl, sizeof(DevCtl), hipMemcpyHostToDevice, s));
+  HIP_CHECK(hipMemcpyAsync(ctl_d + 1, &ctl, sizeof(DevCtl), hipMemcpyHostToDevice, s));
+  HIP_CHECK(hipStreamSynchronize(s));
+  for (size_t i = 0; i < k; i++) {
+    DevCtl* cur = ctl_d + (i & 1);
+    DevCtl* next = ctl_d + 1 - (i & 1);
+    enqueue(i, cur, next);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipMemcpyAsync(snap_ctl_d.p + i, next, sizeof(DevCtl), hipMemcpyDeviceToDevice, s));
+    if (capacity > 0)
+      HIP_CHECK(hipMemcpyAsync(snap_pool_d.p + i * capacity, pool_d, capacity * sizeof(NodeT),
+                               hipMemcpyDeviceToDevice, s));
+  }
+  std::vector<DevCtl> fin(k);
+  HIP_CHECK(hipMemcpyAsync(fin.data(), snap_ctl_d.p, k * sizeof(DevCtl), hipMemcpyDeviceToHost, s));
+  HIP_CHECK(hipStreamSynchronize(s));
+
+  std::vector<DevpoolSnapshot<NodeT>> out(k);
+  // live size entering iteration i, and the un-popped prefix once overflowed:
+  // the overflowing iteration leaves [base, ..) undefined and every later
+  // iteration pops nothing, so that prefix is what all later snapshots keep
+  unsigned long long prev = n, ovf_base = 0;
+  bool overflowed = false;
+  for (size_t i = 0; i < k; i++) {
+    const DevCtl& f = fin[i];
+    unsigned long long keep;
+    if (f.overflow) {
+      if (!overflowed) {
+        const unsigned long long c = prev < m ? 0 : std::min(prev, windows[i]);
+        ovf_base = prev - c;
+        overflowed = true;
+      }
+      keep = ovf_base;
+    } else {
+      if (f.size > capacity) throw std::runtime_error("devpool chain: size exceeds capacity");
+      keep = f.size;
+      prev = f.size;
+    }
+    if (keep > capacity) throw std::runtime_error("devpool chain: prefix exceeds capacity");
+    out[i].nodes.resize(keep);
+    if (keep > 0)
+      HIP_CHECK(hipMemcpyAsync(out[i].nodes.data(), snap_pool_d.p + i * capacity,
+                               keep * sizeof(NodeT), hipMemcpyDeviceToHost, s));
+    out[i].ctl = {f.size, f.chunk, f.tree, f.sol, f.iters, f.best, f.overflow};
+  }
+  HIP_CHECK(hipStreamSynchronize(s));
+  return out;
+}
+
+}  // namespace
+
+std::vector<DevpoolSnapshot<NQNode>> nq_devpool_chain(
+    const std::vector<NQNode>& nodes, int N, int g, int finish, unsigned long long m,
+    const std::vector<unsigned long long>& windows, unsigned long long capacity,
+    const std::string& presum, int device) {
+  validate_nq_step(nodes, N, g, finish, m, 1, capacity, presum);  // before any HIP call
+  validate_chain_windows(windows, N, capacity);
+  const int pm = presum_mode(presum);
+  const unsigned long long Mc = *std::max_element(windows.begin(), windows.end());
+  set_device_cached(device);
+  StreamGuard stream;
+  DevGuard<NQNode> pool_d(std::max<unsigned long long>(capacity, 1));
+  DevGuard<DevCtl> ctl_d(2);
+  // sized ONCE for the largest window, as devpool_thread_nq sizes them for Mc
+  const int G = devpool_grid(Mc, N, 1);
+  const int stride = devpool_stride(1);
+  DevGuard<NQNode> childbuf_d(static_cast<size_t>(G) * stride);
+  DevGuard<uint32_t> bc_d(G);
+  DevGuard<unsigned long long> bs_d(G), be_d(G);
+  const bool presum_alloc = devpool_presum_alloc(G, 1);
+  DevGuard<uint32_t> gsum_d((presum_alloc || pm == 1) ? (G + 255) / 256 : 1);
+  const DevIterBufs<NQNode> bufs{pool_d.p, childbuf_d.p, bc_d.p,  bs_d.p,
+                                 be_d.p,   gsum_d.p,     stride, capacity};
+  return run_chain(nodes, pool_d.p, ctl_d.p, 0, windows, m, capacity, stream.s,
+                   [&](size_t i, DevCtl* cur, DevCtl* next) {
+                     const DevIterPolicy it =
+                         devpool_iter_policy(Mc, windows[i], N, 1, presum_alloc);
+                     const bool ps = pm < 0 ? it.ps : pm == 1;
+                     enqueue_nq_iter(bufs, cur, next, N, g, finish, m, it.Mi, ps, stream.s);
+                   });
+}
+
+std::vector<DevpoolSnapshot<PFSPNode>> pfsp_devpool_chain(
+    const std::vector<PFSPNode>& nodes, int inst, const std::string& lb, int best,
+    unsigned long long m, const std::vector<unsigned long long>& windows,
+    unsigned long long capacity, int geom, const std::string& presum, int device) {
+  validate_pfsp_step(nodes, inst, lb, m, 1, capacity, geom, presum);  // before any HIP call
+  validate_chain_windows(windows, taillard_nb_jobs(inst), capacity);
+  const int pm = presum_mode(presum);
+  const PfspInstance& I = pfsp_instance_cached(inst, 1);
+  const int jobs = I.jobs, machines = I.machines;
+  const int lbg = geom < 0 ? devpool_lbk_geom(lbk_of(lb_from_string(lb)), machines) : geom;
+  const unsigned long long Mc = *std::max_element(windows.begin(), windows.end());
+  set_device_cached(device);
+  const PfspDevTables& tb = pfsp_tables_cached(I, device);
+  StreamGuard stream;
+  DevGuard<PFSPNode> pool_d(std::max<unsigned long long>(capacity, 1));
+  DevGuard<DevCtl> ctl_d(2);
+  // sized ONCE for the largest window, as devpool_thread_pfsp sizes them for Mc
+  const int G = devpool_grid(Mc, jobs, lbg);
+  const int stride = devpool_stride(lbg);
+  DevGuard<PFSPNode> childbuf_d(static_cast<size_t>(G) * stride);
+  DevGuard<uint32_t> bc_d(G);
+  DevGuard<unsigned long long> bs_d(G);
+  const bool presum_alloc = devpool_presum_alloc(G, lbg);
+  DevGuard<uint32_t> gsum_d((presum_alloc || pm == 1) ? (G + 255) / 256 : 1);
+  const DevIterBufs<PFSPNode> bufs{pool_d.p, childbuf_d.p, bc_d.p,  bs_d.p,
+                                   nullptr,  gsum_d.p,     stride, capacity};
+  return run_chain(nodes, pool_d.p, ctl_d.p, best, windows, m, capacity, stream.s,
+                   [&](size_t i, DevCtl* cur, DevCtl* next) {
+                     const DevIterPolicy it =
+                         devpool_iter_policy(Mc, windows[i], jobs, lbg, presum_alloc);
+                     const bool ps = pm < 0 ? it.ps : pm == 1;
+                     enqueue_pfsp_iter(bufs, cur, next, jobs, machines, lbg, tb, m, it.Mi, ps,
+                                       stream.s);
+                   });
 }
 
 // ---------------------------------------------------------------------------

@@ -202,6 +202,37 @@ DevpoolStepCtl pfsp_devpool_step(std::vector<PFSPNode>& nodes, int inst, const s
                                  unsigned long long capacity, int geom,
                                  const std::string& presum, int device);
 
+// Chain entry points (kernel-level tests): the step functions' arguments and
+// validation, with `windows` (1..16 per-iteration launch windows) in place of
+// M. The count / sol / extra / group-sum / child buffers are allocated ONCE
+// for max(windows), as an engine thread sizes them for its chunk cap, and
+// iteration i runs enqueue_*_iter(ctl + (i & 1) -> ctl + 1 - (i & 1)) with
+// window windows[i] on one stream with no host synchronisation in between.
+// After every iteration the live control block and pool[0:capacity] are
+// copied device-to-device into a snapshot area; snapshot i is (the first
+// `size` pool nodes, the control block) as iteration i left them. Once a
+// snapshot's overflow flag is set its nodes are the un-popped prefix of the
+// overflowing iteration (all that is defined from then on). presum "auto" is
+// the engine threads' own per-iteration rule (the shared policy helper in
+// engine_gpu.cpp, with the buffers' presum sizing taken from max(windows));
+// "on" / "off" force the groupSums pointer present / null every iteration.
+// A window below the pool size is legal and is that iteration's pop cap.
+// Everything is validated on the host before the first HIP call:
+// capacity * (windows.size() + 1) <= 2^22 nodes, window * branching <= 2^31.
+template <class NodeT>
+struct DevpoolSnapshot {
+  std::vector<NodeT> nodes;
+  DevpoolStepCtl ctl;
+};
+std::vector<DevpoolSnapshot<NQNode>> nq_devpool_chain(
+    const std::vector<NQNode>& nodes, int N, int g, int finish, unsigned long long m,
+    const std::vector<unsigned long long>& windows, unsigned long long capacity,
+    const std::string& presum, int device);
+std::vector<DevpoolSnapshot<PFSPNode>> pfsp_devpool_chain(
+    const std::vector<PFSPNode>& nodes, int inst, const std::string& lb, int best,
+    unsigned long long m, const std::vector<unsigned long long>& windows,
+    unsigned long long capacity, int geom, const std::string& presum, int device);
+
 std::vector<uint8_t> nq_gpu_labels(int N, int g, const std::vector<NQNode>& nodes,
                                    int device);
 std::vector<int32_t> pfsp_gpu_bounds(int inst, const std::string& lb,

@@ -24,6 +24,14 @@ NODE = 24
 NQ_KEY = 21    # depth + board[20]
 PFSP_KEY = 22  # depth + limit1 + prmu[20]
 
+# near-optimal permutations (insertion local search on the CPU bound; makespans
+# 1366 / 1398 / 2388 vs optima 1359 / 1377 / 2297): a leaf below optimum + 200
+GOOD_PERM = {
+    2: [5, 6, 17, 19, 14, 16, 8, 0, 10, 4, 15, 13, 1, 12, 3, 18, 11, 7, 2, 9],
+    14: [2, 11, 19, 15, 17, 9, 7, 5, 1, 6, 10, 12, 13, 0, 14, 8, 3, 16, 18, 4],
+    21: [15, 9, 7, 0, 6, 14, 16, 8, 4, 5, 19, 10, 11, 12, 3, 17, 1, 13, 2, 18],
+}
+
 
 class Step:
     """Expected outcome of one iteration."""
@@ -74,6 +82,17 @@ def random_pfsp_nodes(rng, n, jobs=20, min_depth=0, max_depth=None):
         rng.shuffle(prmu)
         out.append(pfsp_node(rng.randint(min_depth, max_depth), prmu))
     return b"".join(out)
+
+
+def incumbent_pool(inst):
+    """300 random nodes of depth <= 18, then a tail of 64 depth-19 parents (63
+    random ones and the GOOD_PERM one). With windows [64, 64] the first
+    iteration pops leaf parents only and lowers best from optimum + 200 to
+    GOOD_PERM's makespan; the second pops 64 inner nodes and must prune with
+    the lowered value (no depth-19 parent in it: pruning is deterministic)."""
+    r = rng(inst * 1000 + 19)
+    return (random_pfsp_nodes(r, 300, max_depth=18) +
+            random_pfsp_nodes(r, 63, min_depth=19) + pfsp_node(19, GOOD_PERM[inst]))
 
 
 def nq_step(core, pool, N, g=1, finish=8, m=1, M=None, tree=0, sol=0, iters=0):
@@ -168,6 +187,76 @@ def check_overflow(exp, pool_in, pool_out, ctl, what=""):
     assert ctl["overflow"] == 1, (what, ctl)
     nb = len(exp.prefix)
     assert pool_out[:nb] == pool_in[:nb], (what, "un-popped prefix changed")
+
+
+def loop_windows(n, per, Mc, k):
+    """The loop driver's launch windows for k blind iterations after a
+    readback at pool size n: bound_i = n * per^i (branching `per`), clamped to
+    the chunk cap Mc and to at least one node."""
+    assert k >= 1 and per >= 1 and Mc >= 1
+    out, bound = [], max(n, 1)
+    for _ in range(k):
+        out.append(min(bound, Mc))
+        bound = min(bound * per, Mc)
+    return out
+
+
+def oracle_chain(pool0, windows, step_fn, best=0, capacity=None):
+    """The oracle iterated on its own output: the snapshots a correct chain
+    would return (children in oracle order). An iteration whose next size
+    exceeds `capacity` sets the sticky flag: from then on the snapshot is the
+    un-popped prefix and the counters stop."""
+    pool, ctl = pool0, dict(size=len(pool0) // NODE, chunk=0, tree=0, sol=0, iters=0,
+                            best=best, overflow=0)
+    out = []
+    for M in windows:
+        if not ctl["overflow"]:
+            exp = step_fn(pool, M, ctl["tree"], ctl["sol"], ctl["iters"], ctl["best"])
+            if capacity is not None and exp.ctl["size"] > capacity:
+                pool, ctl = exp.prefix, dict(ctl, overflow=1)
+            else:
+                pool, ctl = exp.pool(), dict(exp.ctl)
+        out.append((pool, dict(ctl)))
+    return out
+
+
+def check_chain(core, pool0, snapshots, windows, step_fn, best=0, capacity=None, what=""):
+    """Compare a chain of snapshots [(pool bytes, ctl dict), ...] with the oracle,
+    one transition at a time. The input of transition i is the previous GPU
+    snapshot (pool0 with zero counters and `best` for i = 0), so every
+    transition is compared directly with the CPU oracle: child order inside
+    the pool is not part of the contract, and only the snapshot says which
+    nodes sit in the popped tail. step_fn(pool, M, tree, sol, iters, best)
+    returns the expected Step. With `capacity` given, the overflow flag must
+    be set exactly when the oracle's next size exceeds it; once set it must
+    stay set and the un-popped prefix must never change again. Returns the
+    list of expected Steps (None for transitions after the overflow). `core`
+    is the bindings module the snapshots came from; the oracle itself reaches
+    the CPU bindings through step_fn."""
+    assert len(snapshots) == len(windows), (what, len(snapshots), len(windows))
+    pool, ctl = pool0, dict(tree=0, sol=0, iters=0, best=best, overflow=0)
+    exps = []
+    for i, ((pool_out, ctl_out), M) in enumerate(zip(snapshots, windows)):
+        w = (what, "iteration", i, "window", M)
+        if ctl["overflow"]:
+            # sticky: nothing is popped or pushed any more
+            check_overflow(Step(pool, [], None, None), pool, pool_out, ctl_out, w)
+            assert len(pool_out) == len(pool), (w, "prefix length changed", len(pool_out))
+            exps.append(None)
+        else:
+            exp = step_fn(pool, M, ctl["tree"], ctl["sol"], ctl["iters"], ctl["best"])
+            over = ctl_out["overflow"] != 0
+            if capacity is not None:
+                assert over == (exp.ctl["size"] > capacity), (w, "overflow flag", ctl_out,
+                                                              exp.ctl, capacity)
+            if over:
+                check_overflow(exp, pool, pool_out, ctl_out, w)
+                assert len(pool_out) == len(exp.prefix), (w, "prefix length", len(pool_out))
+            else:
+                check_step(exp, pool_out, ctl_out, w)
+            exps.append(exp)
+        pool, ctl = pool_out, ctl_out
+    return exps
 
 
 def rng(seed):

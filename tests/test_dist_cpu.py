@@ -33,6 +33,8 @@ def test_dist_gloo(world):
     env = dict(os.environ)
     env.pop("RANK", None)
     env.pop("WORLD_SIZE", None)
+    # CPU tensors need gloo; on a machine WITH a GPU init_dist would pick nccl
+    env["GATS_DIST_BACKEND"] = "gloo"
     cmd = [
         sys.executable, "-m", "torch.distributed.run",
         "--nnodes=1", f"--nproc-per-node={world}",
@@ -51,6 +53,8 @@ def test_live_steal_gloo(world):
     env = dict(os.environ)
     env.pop("RANK", None)
     env.pop("WORLD_SIZE", None)
+    # CPU tensors need gloo; on a machine WITH a GPU init_dist would pick nccl
+    env["GATS_DIST_BACKEND"] = "gloo"
     cmd = [
         sys.executable, "-m", "torch.distributed.run",
         "--nnodes=1", f"--nproc-per-node={world}",

@@ -26,13 +26,7 @@ INSTS = [2, 14, 21]  # 20x5, 20x10, 20x20
 # (lb, geom): every PFSP expand kernel; both lb2 geometries on every machine count
 KERNELS = [("lb1", -1), ("lb1_d", -1), ("lb2", 3), ("lb2", 2)]
 KERNEL_IDS = ["lb1", "lb1_d", "lb2-lane", "lb2-wave"]
-# near-optimal permutations (insertion local search on the CPU bound; makespans
-# 1366 / 1398 / 2388 vs optima 1359 / 1377 / 2297): a leaf below optimum + 200
-GOOD_PERM = {
-    2: [5, 6, 17, 19, 14, 16, 8, 0, 10, 4, 15, 13, 1, 12, 3, 18, 11, 7, 2, 9],
-    14: [2, 11, 19, 15, 17, 9, 7, 5, 1, 6, 10, 12, 13, 0, 14, 8, 3, 16, 18, 4],
-    21: [15, 9, 7, 0, 6, 14, 16, 8, 4, 5, 19, 10, 11, 12, 3, 17, 1, 13, 2, 18],
-}
+GOOD_PERM = orc.GOOD_PERM
 
 _oracle_cache = {}
 
