@@ -3,6 +3,7 @@
 Flags parity (reference config consts + common_help_message, util.chpl:32-40):
   --N --g (N-Queens, nqueens_chpl.chpl:15-16), --inst --lb --ub (PFSP,
   pfsp_chpl.chpl:20-22), --m --M --D (offload window / device count).
+Beyond the reference: --br (PFSP branching rule; the reference is fwd only).
 Output parity: print_settings / per-phase blocks / print_results
 (pfsp_gpu_chpl.chpl:54-77, nqueens_gpu_chpl.chpl:30-46) plus GPU diagnostics
 (GpuDiagnostics parity, nqueens_gpu_chpl.chpl:278-282).
@@ -115,6 +116,10 @@ def main(argv=None):
     pf.add_argument("--lb", default="lb1", choices=["lb1", "lb1_d", "lb2"])
     pf.add_argument("--ub", type=int, default=1, choices=[0, 1],
                     help="initial upper bound: 1=known optimum, 0=inf")
+    pf.add_argument("--br", default="fwd", choices=["fwd", "bwd", "alt", "minbranch"],
+                    help="branching rule: fwd (reference), bwd, alt (by depth parity), "
+                         "minbranch (per node, the side with fewer surviving children; "
+                         "lb1_d only). Non-fwd rules: tiers seq and gpu (gpu: lb1_d)")
     add_common(pf)
 
     args = ap.parse_args(argv)
@@ -154,6 +159,13 @@ def main(argv=None):
             _stats_line(args.stats_file, args, r)
     else:
         inst = args.inst
+        if args.br != "fwd" and args.tier in ("multigpu", "dist"):
+            ap.error(f"--br {args.br} is not yet supported on tier {args.tier} "
+                     "(fwd only; use --tier seq or --tier gpu)")
+        if args.br == "minbranch" and args.lb != "lb1_d":
+            ap.error("--br minbranch needs --lb lb1_d")
+        if args.br != "fwd" and args.tier == "gpu" and args.lb != "lb1_d":
+            ap.error(f"--br {args.br} on tier gpu needs --lb lb1_d")
         jobs, machines = c.taillard_nb_jobs(inst), c.taillard_nb_machines(inst)
         init_ub = c.taillard_best_ub(inst) if args.ub == 1 else float("inf")
         tier_name = {"seq": "Sequential", "gpu": "Single-GPU", "multigpu": "Multi-GPU",
@@ -163,13 +175,13 @@ def main(argv=None):
                  f"(m = {machines}, n = {jobs})",
                  "Initial upper bound: " + ("opt" if args.ub == 1 else "inf"),
                  f"Lower bound function: {args.lb}",
-                 "Branching rule: fwd"])
+                 f"Branching rule: {args.br}"])
         if args.tier == "seq":
-            r = c.pfsp_seq(inst, args.lb, args.ub)
+            r = c.pfsp_seq(inst, args.lb, args.ub, br=args.br)
         elif args.tier == "gpu":
             gats_amd.require_gpu()
             r = c.pfsp_gpu(inst, args.lb, args.ub, args.m, args.M, 0, args.mode,
-                           args.capacity)
+                           args.capacity, br=args.br)
             _phases(r)
         elif args.tier == "multigpu":
             gats_amd.require_gpu()

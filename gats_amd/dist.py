@@ -558,6 +558,9 @@ def run_from_cli(args):
     the tier with the CPU evaluator (CI coverage of the full CLI dist path
     without a GPU; the ub=0 mid-search UB exchange needs the GPU engine and
     falls back to the end-of-search min-reduce)."""
+    if getattr(args, "br", "fwd") != "fwd":
+        raise ValueError(f"branching rule '{args.br}' is not yet supported on the dist tier "
+                         "(fwd only)")
     rank, world = init_dist()
     engine = os.environ.get("GATS_DIST_ENGINE", "gpu")
     live = os.environ.get("GATS_DIST_LIVE") == "1"

@@ -109,6 +109,31 @@ std::vector<int32_t> pfsp_cpu_bounds(int inst, const std::string& lb_str,
   return bounds;
 }
 
+// Both-directions lb1_d child bounds (same layout as pfsp_gpu_bounds_bi): by
+// position, -1 outside the parent's unscheduled range.
+py::tuple pfsp_cpu_bounds_bi(int inst, const py::bytes& pool_bytes) {
+  PfspInstance I = make_pfsp_instance(inst, 1);
+  auto nodes = nodes_from_bytes<PFSPNode>(pool_bytes);
+  std::vector<int32_t> lb_begin(nodes.size() * I.jobs, -1), lb_end(nodes.size() * I.jobs, -1);
+  for (size_t i = 0; i < nodes.size(); i++) {
+    const PFSPNode& p = nodes[i];
+    const int limit2 = I.jobs - p.nback;
+    if (p.limit1 < -1 || p.limit1 + 1 > limit2)
+      throw std::invalid_argument("node " + std::to_string(i) +
+                                  ": limit1 + 1 + nback exceeds jobs");
+    for (int j = 0; j < I.jobs; j++)
+      if (p.prmu[j] >= I.jobs)
+        throw std::invalid_argument("node " + std::to_string(i) + ": prmu entry >= jobs");
+    int b[MAX_JOBS], e[MAX_JOBS];
+    lb1_children_bounds_bi(I.lb1, p.prmu, p.limit1, limit2, b, e);
+    for (int k = p.limit1 + 1; k < limit2; k++) {
+      lb_begin[i * I.jobs + k] = b[p.prmu[k]];
+      lb_end[i * I.jobs + k] = e[p.prmu[k]];
+    }
+  }
+  return py::make_tuple(lb_begin, lb_end);
+}
+
 py::tuple nq_bfs_frontier(int N, int g, size_t target) {
   Pool<NQNode> pool;
   pool.pushBack(nq_root());
@@ -134,9 +159,11 @@ py::tuple nq_gpu_frontier_py(int N, int g, size_t target, int device) {
 }
 
 py::tuple pfsp_gpu_frontier_py(int inst, const std::string& lb_str, int ub, size_t target,
-                               int device) {
+                               int device, const std::string& br_str) {
   const LbKind lb = lb_from_string(lb_str);
-  PfspInstance I = make_pfsp_instance(inst, ub);
+  const Branching br = branching_from_string(br_str);
+  check_branching_supported(lb, br, true);
+  PfspInstance I = make_pfsp_instance(inst, ub, br);
   const int lbk = (lb == LbKind::LB1_D) ? 0 : (lb == LbKind::LB1 ? 1 : 2);
   uint64_t tree = 0, sol = 0;
   int best = I.init_ub;
@@ -148,9 +175,12 @@ py::tuple pfsp_gpu_frontier_py(int inst, const std::string& lb_str, int ub, size
   return py::make_tuple(nodes_to_bytes(nodes.data(), nodes.size()), tree, sol, best);
 }
 
-py::tuple pfsp_bfs_frontier(int inst, const std::string& lb_str, int ub, size_t target) {
+py::tuple pfsp_bfs_frontier(int inst, const std::string& lb_str, int ub, size_t target,
+                            const std::string& br_str) {
   const LbKind lb = lb_from_string(lb_str);
-  PfspInstance I = make_pfsp_instance(inst, ub);
+  const Branching br = branching_from_string(br_str);
+  check_branching_supported(lb, br, false);
+  PfspInstance I = make_pfsp_instance(inst, ub, br);
   Pool<PFSPNode> pool;
   pool.pushBack(pfsp_root());
   uint64_t tree = 0, sol = 0;
@@ -178,13 +208,16 @@ py::dict nqueens_seq_from_pool(const py::bytes& nodes, int N, int g) {
 }
 
 py::dict pfsp_seq_from_pool(const py::bytes& nodes, int inst, const std::string& lb_str,
-                            int ub, int best0) {
+                            int ub, int best0, const std::string& br_str) {
   auto v = nodes_from_bytes<PFSPNode>(nodes);
   const LbKind lb = lb_from_string(lb_str);
+  const Branching br = branching_from_string(br_str);
+  check_branching_supported(lb, br, false);
+  check_pfsp_pool(v.data(), v.size(), br);
   Result r;
   {
     py::gil_scoped_release rel;
-    PfspInstance I = make_pfsp_instance(inst, ub);
+    PfspInstance I = make_pfsp_instance(inst, ub, br);
     int best = (best0 > 0) ? best0 : I.init_ub;
     Pool<PFSPNode> pool;
     pool.pushBackBulk(v.data(), v.size());
@@ -203,15 +236,18 @@ py::dict pfsp_seq_from_pool(const py::bytes& nodes, int inst, const std::string&
 // dist tier's CPU mock engine uses it so a stale incumbent is re-read every
 // few ms instead of once per whole subtree).
 py::tuple pfsp_seq_step(const py::bytes& nodes, int inst, const std::string& lb_str,
-                        int ub, int best0, uint64_t max_nodes) {
+                        int ub, int best0, uint64_t max_nodes, const std::string& br_str) {
   auto v = nodes_from_bytes<PFSPNode>(nodes);
   const LbKind lb = lb_from_string(lb_str);
+  const Branching br = branching_from_string(br_str);
+  check_branching_supported(lb, br, false);
+  check_pfsp_pool(v.data(), v.size(), br);
   uint64_t tree = 0, sol = 0;
   int best;
   Pool<PFSPNode> pool;
   {
     py::gil_scoped_release rel;
-    PfspInstance I = make_pfsp_instance(inst, ub);
+    PfspInstance I = make_pfsp_instance(inst, ub, br);
     best = (best0 > 0) ? best0 : I.init_ub;
     pool.pushBackBulk(v.data(), v.size());
     PFSPNode parent;
@@ -261,7 +297,8 @@ py::tuple nq_devpool_step_py(const py::bytes& nodes, int N, int g, int finish, l
 py::tuple pfsp_devpool_step_py(const py::bytes& nodes, int inst, const std::string& lb,
                                int best, long long m, const py::object& M,
                                const py::object& capacity, int geom,
-                               const std::string& presum, int device) {
+                               const std::string& presum, int device,
+                               const std::string& br) {
   auto v = nodes_from_bytes<PFSPNode>(nodes);
   if (m < 0) throw std::invalid_argument("m must be >= 1");
   const unsigned long long Mv = step_arg(M, v.empty() ? 1 : v.size(), "M");
@@ -270,7 +307,7 @@ py::tuple pfsp_devpool_step_py(const py::bytes& nodes, int inst, const std::stri
   {
     py::gil_scoped_release rel;
     c = pfsp_devpool_step(v, inst, lb, best, static_cast<unsigned long long>(m), Mv, cap,
-                          geom, presum, device);
+                          geom, presum, device, br);
   }
   return py::make_tuple(nodes_to_bytes(v.data(), v.size()), step_ctl_to_dict(c));
 }
@@ -314,7 +351,7 @@ py::list nq_devpool_chain_py(const py::bytes& nodes, int N, const std::vector<lo
 py::list pfsp_devpool_chain_py(const py::bytes& nodes, int inst, const std::string& lb,
                                int best, const std::vector<long long>& windows, long long m,
                                const py::object& capacity, int geom, const std::string& presum,
-                               int device) {
+                               int device, const std::string& br) {
   auto v = nodes_from_bytes<PFSPNode>(nodes);
   if (m < 0) throw std::invalid_argument("m must be >= 1");
   const auto w = chain_windows(windows);
@@ -323,7 +360,7 @@ py::list pfsp_devpool_chain_py(const py::bytes& nodes, int inst, const std::stri
   {
     py::gil_scoped_release rel;
     snaps = pfsp_devpool_chain(v, inst, lb, best, static_cast<unsigned long long>(m), w, cap,
-                               geom, presum, device);
+                               geom, presum, device, br);
   }
   return chain_to_list(snaps);
 }
@@ -373,15 +410,16 @@ PYBIND11_MODULE(_core, mod) {
           },
           py::arg("N") = 14, py::arg("g") = 1);
   mod.def("pfsp_seq",
-          [](int inst, const std::string& lb, int ub) {
+          [](int inst, const std::string& lb, int ub, const std::string& br) {
             Result r;
             {
               py::gil_scoped_release rel;
-              r = pfsp_seq(inst, lb, ub);
+              r = pfsp_seq(inst, lb, ub, br);
             }
             return result_to_dict(r);
           },
-          py::arg("inst") = 14, py::arg("lb") = "lb1", py::arg("ub") = 1);
+          py::arg("inst") = 14, py::arg("lb") = "lb1", py::arg("ub") = 1,
+          py::arg("br") = "fwd");
 
   mod.def("gpu_device_count", &gpu_device_count);
 
@@ -401,18 +439,18 @@ PYBIND11_MODULE(_core, mod) {
   mod.def("pfsp_multigpu",
           [](int inst, const std::string& lb, int ub, int m, int M, int D,
              const std::string& eval, bool share_best, double perc,
-             unsigned long long capacity) {
+             unsigned long long capacity, const std::string& br) {
             Result r;
             {
               py::gil_scoped_release rel;
-              r = pfsp_multigpu(inst, lb, ub, m, M, D, eval, share_best, perc, capacity);
+              r = pfsp_multigpu(inst, lb, ub, m, M, D, eval, share_best, perc, capacity, br);
             }
             return result_to_dict(r);
           },
           py::arg("inst") = 14, py::arg("lb") = "lb1", py::arg("ub") = 1, py::arg("m") = 25,
           py::arg("M") = 50000, py::arg("D") = 1, py::arg("eval") = "gpu",
           py::arg("share_best") = false, py::arg("perc") = 0.5,
-          py::arg("capacity") = (1ull << 27));
+          py::arg("capacity") = (1ull << 27), py::arg("br") = "fwd");
 
   mod.def("nqueens_gpu",
           [](int N, int g, int m, int M, int device, const std::string& mode,
@@ -430,17 +468,17 @@ PYBIND11_MODULE(_core, mod) {
 
   mod.def("pfsp_gpu",
           [](int inst, const std::string& lb, int ub, int m, int M, int device,
-             const std::string& mode, unsigned long long capacity) {
+             const std::string& mode, unsigned long long capacity, const std::string& br) {
             Result r;
             {
               py::gil_scoped_release rel;
-              r = pfsp_gpu(inst, lb, ub, m, M, device, mode, capacity);
+              r = pfsp_gpu(inst, lb, ub, m, M, device, mode, capacity, br);
             }
             return result_to_dict(r);
           },
           py::arg("inst") = 14, py::arg("lb") = "lb1", py::arg("ub") = 1, py::arg("m") = 25,
           py::arg("M") = 50000, py::arg("device") = 0, py::arg("mode") = "devpool",
-          py::arg("capacity") = (1ull << 27));
+          py::arg("capacity") = (1ull << 27), py::arg("br") = "fwd");
 
   mod.def("nqueens_gpu_rooted",
           [](int N, int g, int M, int device, unsigned long long capacity) {
@@ -456,17 +494,17 @@ PYBIND11_MODULE(_core, mod) {
 
   mod.def("pfsp_gpu_rooted",
           [](int inst, const std::string& lb, int ub, int M, int device,
-             unsigned long long capacity) {
+             unsigned long long capacity, const std::string& br) {
             Result r;
             {
               py::gil_scoped_release rel;
-              r = pfsp_gpu_rooted(inst, lb, ub, M, device, capacity);
+              r = pfsp_gpu_rooted(inst, lb, ub, M, device, capacity, br);
             }
             return result_to_dict(r);
           },
           py::arg("inst") = 14, py::arg("lb") = "lb1", py::arg("ub") = 1,
           py::arg("M") = 50000, py::arg("device") = 0,
-          py::arg("capacity") = (1ull << 27));
+          py::arg("capacity") = (1ull << 27), py::arg("br") = "fwd");
 
   mod.def("nqueens_gpu_from_pool",
           [](const py::bytes& nodes, int N, int g, int m, int M, int device,
@@ -486,40 +524,50 @@ PYBIND11_MODULE(_core, mod) {
   mod.def("pfsp_gpu_from_pool",
           [](const py::bytes& nodes, int inst, const std::string& lb, int ub, int best0,
              int m, int M, int device, const std::string& mode,
-             unsigned long long capacity) {
+             unsigned long long capacity, const std::string& br) {
             auto v = nodes_from_bytes<PFSPNode>(nodes);
             Result r;
             {
               py::gil_scoped_release rel;
-              r = pfsp_gpu_from_pool(v, inst, lb, ub, best0, m, M, device, mode, capacity);
+              r = pfsp_gpu_from_pool(v, inst, lb, ub, best0, m, M, device, mode, capacity,
+                                     br);
             }
             return result_to_dict(r);
           },
           py::arg("nodes"), py::arg("inst"), py::arg("lb") = "lb1", py::arg("ub") = 1,
           py::arg("best0") = 0, py::arg("m") = 25, py::arg("M") = 50000,
           py::arg("device") = 0, py::arg("mode") = "devpool",
-          py::arg("capacity") = (1ull << 27));
+          py::arg("capacity") = (1ull << 27), py::arg("br") = "fwd");
 
   mod.def("pfsp_seq_step", &pfsp_seq_step, py::arg("nodes"), py::arg("inst"),
           py::arg("lb") = "lb1", py::arg("ub") = 1, py::arg("best0") = 0,
-          py::arg("max_nodes") = 50000);
+          py::arg("max_nodes") = 50000, py::arg("br") = "fwd");
   mod.def("nqueens_seq_from_pool", &nqueens_seq_from_pool, py::arg("nodes"), py::arg("N"),
           py::arg("g") = 1);
   mod.def("pfsp_seq_from_pool", &pfsp_seq_from_pool, py::arg("nodes"), py::arg("inst"),
-          py::arg("lb") = "lb1", py::arg("ub") = 1, py::arg("best0") = 0);
+          py::arg("lb") = "lb1", py::arg("ub") = 1, py::arg("best0") = 0,
+          py::arg("br") = "fwd");
 
   mod.def("nq_bfs_frontier", &nq_bfs_frontier, py::arg("N"), py::arg("g") = 1,
           py::arg("target") = 1024);
   mod.def("pfsp_bfs_frontier", &pfsp_bfs_frontier, py::arg("inst"), py::arg("lb") = "lb1",
-          py::arg("ub") = 1, py::arg("target") = 1024);
+          py::arg("ub") = 1, py::arg("target") = 1024, py::arg("br") = "fwd");
   mod.def("nq_gpu_frontier", &nq_gpu_frontier_py, py::arg("N"), py::arg("g") = 1,
           py::arg("target") = 1024, py::arg("device") = 0);
   mod.def("pfsp_gpu_frontier", &pfsp_gpu_frontier_py, py::arg("inst"),
           py::arg("lb") = "lb1", py::arg("ub") = 1, py::arg("target") = 1024,
-          py::arg("device") = 0);
+          py::arg("device") = 0, py::arg("br") = "fwd");
 
   mod.def("nq_cpu_labels", &nq_cpu_labels);
   mod.def("pfsp_cpu_bounds", &pfsp_cpu_bounds);
+  mod.def("pfsp_cpu_bounds_bi", &pfsp_cpu_bounds_bi, py::arg("inst"), py::arg("nodes"));
+  mod.def("pfsp_gpu_bounds_bi",
+          [](int inst, const py::bytes& nodes, int device) {
+            auto v = nodes_from_bytes<PFSPNode>(nodes);
+            auto r = pfsp_gpu_bounds_bi(inst, v, device);
+            return py::make_tuple(r.first, r.second);
+          },
+          py::arg("inst"), py::arg("nodes"), py::arg("device") = 0);
   mod.def("nq_gpu_labels",
           [](int N, int g, const py::bytes& nodes, int device) {
             auto v = nodes_from_bytes<NQNode>(nodes);
@@ -542,7 +590,7 @@ PYBIND11_MODULE(_core, mod) {
   mod.def("pfsp_devpool_step", &pfsp_devpool_step_py, py::arg("nodes"), py::arg("inst"),
           py::arg("lb"), py::arg("best"), py::arg("m") = 1, py::arg("M") = py::none(),
           py::arg("capacity") = py::none(), py::arg("geom") = -1,
-          py::arg("presum") = "auto", py::arg("device") = 0);
+          py::arg("presum") = "auto", py::arg("device") = 0, py::arg("br") = "fwd");
   mod.def("nq_devpool_chain", &nq_devpool_chain_py, py::arg("nodes"), py::arg("N"),
           py::arg("windows"), py::arg("g") = 1, py::arg("finish") = 8, py::arg("m") = 1,
           py::arg("capacity") = py::none(), py::arg("presum") = "auto",
@@ -550,7 +598,7 @@ PYBIND11_MODULE(_core, mod) {
   mod.def("pfsp_devpool_chain", &pfsp_devpool_chain_py, py::arg("nodes"), py::arg("inst"),
           py::arg("lb"), py::arg("best"), py::arg("windows"), py::arg("m") = 1,
           py::arg("capacity") = py::none(), py::arg("geom") = -1,
-          py::arg("presum") = "auto", py::arg("device") = 0);
+          py::arg("presum") = "auto", py::arg("device") = 0, py::arg("br") = "fwd");
 
   mod.def("pool_selftest", &pool_selftest);
   // pure policy helpers (CPU-unit-testable): kernel geometry selection and
@@ -565,20 +613,22 @@ PYBIND11_MODULE(_core, mod) {
                               "exchange), engine-pausing work extraction for inter-rank "
                               "steals")
       .def(py::init([](const py::bytes& nodes, int inst, const std::string& lb, int ub,
-                       int best0, int m, int M, int device, unsigned long long capacity) {
+                       int best0, int m, int M, int device, unsigned long long capacity,
+                       const std::string& br) {
              return new PfspAsyncEngine(nodes_from_bytes<PFSPNode>(nodes), inst, lb, ub,
-                                        best0, m, M, device, capacity);
+                                        best0, m, M, device, capacity, br);
            }),
            py::arg("nodes"), py::arg("inst"), py::arg("lb") = "lb1", py::arg("ub") = 1,
            py::arg("best0") = 0, py::arg("m") = 25, py::arg("M") = 50000,
-           py::arg("device") = 0, py::arg("capacity") = (1ull << 24))
+           py::arg("device") = 0, py::arg("capacity") = (1ull << 24),
+           py::arg("br") = "fwd")
       .def(py::init([](int inst, const std::string& lb, int ub, int m, int M, int device,
-                       unsigned long long capacity) {
-             return new PfspAsyncEngine(inst, lb, ub, m, M, device, capacity);
+                       unsigned long long capacity, const std::string& br) {
+             return new PfspAsyncEngine(inst, lb, ub, m, M, device, capacity, br);
            }),
            py::arg("inst"), py::arg("lb") = "lb1", py::arg("ub") = 1, py::arg("m") = 25,
            py::arg("M") = 50000, py::arg("device") = 0,
-           py::arg("capacity") = (1ull << 24))
+           py::arg("capacity") = (1ull << 24), py::arg("br") = "fwd")
       .def("submit",
            [](PfspAsyncEngine& e, const py::bytes& nodes, int best0) {
              e.submit(nodes_from_bytes<PFSPNode>(nodes), best0);

@@ -81,6 +81,24 @@ int add_front_and_bound(const Lb1Data& d, int job, const int* front, const int* 
   return lb;
 }
 
+// Mirror image of add_front_and_bound: schedule `job` in front of the back
+// partial schedule (c_bound_simple.c:246-275). The machine loop runs in
+// descending order with the roles of front and back swapped.
+int add_back_and_bound(const Lb1Data& d, int job, const int* front, const int* back,
+                       const int* remain) {
+  const int n = d.jobs, m = d.machines;
+  const int* p = d.p_times.data();
+  const int last = m - 1;
+  int lb = front[last] + remain[last] + back[last];
+  int tmp0 = back[last] + p[last * n + job];
+  for (int i = last - 1; i >= 0; i--) {
+    int tmp1 = imax(tmp0, back[i]);
+    lb = imax(lb, tmp1 + remain[i] + front[i]);
+    tmp0 = tmp1 + p[i * n + job];
+  }
+  return lb;
+}
+
 }  // namespace
 
 Lb1Data make_lb1_data_from_ptm(const std::vector<int>& p_times, int jobs, int machines) {
@@ -192,6 +210,21 @@ void lb1_children_bounds(const Lb1Data& d, const uint8_t* prmu, int limit1, int 
   for (int i = limit1 + 1; i < limit2; i++) {
     int job = prmu[i];
     lb_out[job] = add_front_and_bound(d, job, front, back, remain);
+  }
+}
+
+void lb1_children_bounds_bi(const Lb1Data& d, const uint8_t* prmu, int limit1, int limit2,
+                            int* lb_begin, int* lb_end) {
+  int front[64], back[64], remain[64];
+  schedule_front(d, prmu, limit1, front);
+  schedule_back(d, prmu, limit2, back);
+  sum_unscheduled(d, prmu, limit1, limit2, remain);
+  if (lb_begin) std::memset(lb_begin, 0, sizeof(int) * d.jobs);
+  if (lb_end) std::memset(lb_end, 0, sizeof(int) * d.jobs);
+  for (int i = limit1 + 1; i < limit2; i++) {
+    const int job = prmu[i];
+    if (lb_begin) lb_begin[job] = add_front_and_bound(d, job, front, back, remain);
+    if (lb_end) lb_end[job] = add_back_and_bound(d, job, front, back, remain);
   }
 }
 

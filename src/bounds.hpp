@@ -43,15 +43,24 @@ Lb1Data make_lb1_data_from_ptm(const std::vector<int>& p_times, int jobs, int ma
 Lb2Data make_lb2_data(const Lb1Data& lb1);
 
 // O(m*n) one-machine bound of the prefix [0, limit1] of prmu
-// (c_bound_simple.c:143-158). limit2 is always jobs in this framework
-// (forward branching only), which makes the back schedule the constant
-// min_tails vector.
+// (c_bound_simple.c:143-158) and of the suffix [limit2, jobs). Under forward
+// branching limit2 is always jobs, which makes the back schedule the constant
+// min_tails vector; backward / dynamic branching passes
+// limit2 = jobs - nback.
 int lb1_bound(const Lb1Data& d, const uint8_t* prmu, int limit1, int limit2);
 
 // Bounds of ALL children of a parent at once, O(m) incremental per child;
 // the "lb1_d" variant (c_bound_simple.c:160-244). lb_out is indexed by JOB id.
 void lb1_children_bounds(const Lb1Data& d, const uint8_t* prmu, int limit1, int limit2,
                          int* lb_out);
+
+// Both-directions variant (backward / dynamic branching): lb_begin[job] is the
+// bound of the child that schedules `job` right after the front partial
+// schedule (add_front_and_bound), lb_end[job] of the child that schedules it
+// right before the back partial schedule (add_back_and_bound,
+// c_bound_simple.c:246-275). Either output may be null (direction skipped).
+void lb1_children_bounds_bi(const Lb1Data& d, const uint8_t* prmu, int limit1, int limit2,
+                            int* lb_begin, int* lb_end);
 
 // Johnson two-machine bound with early exit when the bound exceeds best_cmax
 // (c_bound_johnson.c:211-254).

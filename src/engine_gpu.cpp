@@ -24,6 +24,7 @@
 #include <deque>
 #include <functional>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <thread>
 #include <cstring>
@@ -160,6 +161,8 @@ struct PfspTablesGuard {
         keep(dev_upload(pk.jp_w.data(), pk.jp_w.size()), pk.jp_w.size() * sizeof(uint32_t));
     tb.pairs1_w = keep(dev_upload(pk.p1_w.data(), pk.p1_w.size()), pk.p1_w.size());
     tb.pairs2_w = keep(dev_upload(pk.p2_w.data(), pk.p2_w.size()), pk.p2_w.size());
+    std::vector<int32_t> mh(I.lb1.min_heads.begin(), I.lb1.min_heads.end());
+    tb.min_heads = keep(dev_upload(mh.data(), mh.size()), mh.size() * sizeof(mh[0]));
   }
   std::vector<size_t> alloc_bytes;
   template <typename T>
@@ -428,9 +431,9 @@ void enqueue_nq_iter(const DevIterBufs<NQNode>& b, DevCtl* cur, DevCtl* next, in
 
 void enqueue_pfsp_iter(const DevIterBufs<PFSPNode>& b, DevCtl* cur, DevCtl* next, int jobs,
                        int machines, int lbg, const PfspDevTables& tb, unsigned long long m,
-                       unsigned long long Mi, bool presum, hipStream_t s) {
+                       unsigned long long Mi, bool presum, hipStream_t s, int br = 0) {
   const int Gi = devpool_grid(Mi, jobs, lbg);
-  launch_pfsp_x(cur, b.pool, b.childbuf, b.bc, b.bs, jobs, machines, lbg, tb, m, Mi, s);
+  launch_pfsp_x(cur, b.pool, b.childbuf, b.bc, b.bs, jobs, machines, lbg, tb, m, Mi, s, br);
   if (presum) launch_presum(b.bc, b.gsum, Gi, s);
   launch_gather2_pfsp(cur, next, b.bc, b.bs, presum ? b.gsum : nullptr, b.childbuf, b.pool,
                       b.stride, Gi, m, Mi, b.capacity, s);
@@ -990,7 +993,7 @@ static SliceOut devpool_thread_pfsp(const std::vector<std::vector<PFSPNode>>& sl
   auto iter = [&](int parity, unsigned long long bound) {
     const DevIterPolicy it = devpool_iter_policy(Mc, bound, jobs, lbg, presum);
     enqueue_pfsp_iter(bufs, ctl_d.p + parity, ctl_d.p + (1 - parity), jobs, machines, lbg, tb,
-                      m, it.Mi, it.ps, stream.s);
+                      m, it.Mi, it.ps, stream.s, static_cast<int>(I.br));
   };
   ReadbackHook hook = [&](DevCtl* hc, DevCtl* live) {
     donate_if_wanted(share, hc, live, pool_d.p, m, stream.s);
@@ -1209,6 +1212,9 @@ DevpoolMultiOut pfsp_devpool_multi(const PfspInstance& I, Pool<PFSPNode>& pool, 
   const int jobs = I.jobs;
   if (static_cast<unsigned long long>(M) * jobs > (1ull << 31))
     throw std::invalid_argument("devpool requires M * jobs <= 2^31");
+  if (I.br != Branching::FWD && lbk != 0)
+    throw std::invalid_argument(std::string("branching rule '") + branching_name(I.br) +
+                                "' on the gpu tier needs lb1_d");
   const int D = static_cast<int>(devices.size());
   int S = devpool_slices(devpool_lbk_geom(lbk, I.machines));
   int maxd = 0;  // same deep-frontier rule as N-Queens (12+ open jobs)
@@ -1380,23 +1386,41 @@ Result pfsp_gpu_run(const PfspInstance& I, LbKind lb, Pool<PFSPNode>& pool, int 
     PinnedGuard<int32_t> bounds(static_cast<size_t>(M) * jobs);
     DevGuard<PFSPNode> parents_d(M);
     DevGuard<int32_t> bounds_d(static_cast<size_t>(M) * jobs);
+    // non-fwd branching rules: the kernel returns both directions' bounds
+    // (lb_begin in bounds, lb_end in bounds2) and the host picks per parent
+    const bool bi = I.br != Branching::FWD;
+    if (bi) check_branching_supported(lb, I.br, true);
+    std::unique_ptr<PinnedGuard<int32_t>> bounds2;
+    std::unique_ptr<DevGuard<int32_t>> bounds2_d;
+    if (bi) {
+      bounds2.reset(new PinnedGuard<int32_t>(static_cast<size_t>(M) * jobs));
+      bounds2_d.reset(new DevGuard<int32_t>(static_cast<size_t>(M) * jobs));
+    }
     while (true) {
       const size_t n = pool.popBackBulk(m, M, parents.p);
       if (n == 0) break;
       HIP_CHECK(hipMemcpyAsync(parents_d.p, parents.p, n * sizeof(PFSPNode),
                                hipMemcpyHostToDevice, stream.s));
       launch_pfsp_eval(parents_d.p, static_cast<int>(n), jobs, machines, lbk, tb_dev, best,
-                       bounds_d.p, stream.s);
+                       bounds_d.p, stream.s, static_cast<int>(I.br),
+                       bi ? bounds2_d->p : nullptr);
       HIP_CHECK(hipMemcpyAsync(bounds.p, bounds_d.p, n * jobs * sizeof(int32_t),
                                hipMemcpyDeviceToHost, stream.s));
+      if (bi)
+        HIP_CHECK(hipMemcpyAsync(bounds2->p, bounds2_d->p, n * jobs * sizeof(int32_t),
+                                 hipMemcpyDeviceToHost, stream.s));
       HIP_CHECK(hipStreamSynchronize(stream.s));
       r.kernel_launch++;
       r.h2d++;
-      r.d2h++;
+      r.d2h += bi ? 2 : 1;
       r.h2d_bytes += n * sizeof(PFSPNode);
-      r.d2h_bytes += n * jobs * sizeof(int32_t);
+      r.d2h_bytes += (bi ? 2 : 1) * n * jobs * sizeof(int32_t);
       r.gpu_iters++;
-      pfsp_generate_children(I, parents.p, n, bounds.p, tree, sol, best, pool);
+      if (bi)
+        pfsp_generate_children_bi(I, parents.p, n, bounds.p, bounds2->p, tree, sol, best,
+                                  pool);
+      else
+        pfsp_generate_children(I, parents.p, n, bounds.p, tree, sol, best, pool);
     }
   } else if (mode == "devpool") {
     DevpoolMultiOut o = pfsp_devpool_multi(I, pool, lbk, best, m, M, {device}, capacity,
@@ -1426,22 +1450,31 @@ Result pfsp_gpu_run(const PfspInstance& I, LbKind lb, Pool<PFSPNode>& pool, int 
 }
 
 // Host-side instance (Taillard matrix + lb1/lb2 tables incl. 190 Johnson
-// sorts) cached per (inst, ub).
-static const PfspInstance& pfsp_instance_cached(int inst, int ub) {
+// sorts) cached per (inst, ub, branching rule).
+static const PfspInstance& pfsp_instance_cached(int inst, int ub,
+                                                Branching br = Branching::FWD) {
   static std::mutex mu;
-  static std::map<std::pair<int, int>, PfspInstance*> cache;
+  static std::map<std::pair<std::pair<int, int>, int>, PfspInstance*> cache;
   std::lock_guard<std::mutex> l(mu);
-  auto key = std::make_pair(inst, ub);
+  auto key = std::make_pair(std::make_pair(inst, ub), static_cast<int>(br));
   auto it = cache.find(key);
   if (it == cache.end())
-    it = cache.emplace(key, new PfspInstance(make_pfsp_instance(inst, ub))).first;
+    it = cache.emplace(key, new PfspInstance(make_pfsp_instance(inst, ub, br))).first;
   return *it->second;
 }
 
+// Parse + validate a branching rule for a GPU-tier entry point.
+static Branching gpu_branching(LbKind lb, const std::string& br_str) {
+  const Branching br = branching_from_string(br_str);
+  check_branching_supported(lb, br, true);
+  return br;
+}
+
 Result pfsp_gpu(int inst, const std::string& lb_str, int ub, int m, int M, int device,
-                const std::string& mode, unsigned long long capacity) {
+                const std::string& mode, unsigned long long capacity,
+                const std::string& br) {
   const LbKind lb = lb_from_string(lb_str);
-  const PfspInstance& I = pfsp_instance_cached(inst, ub);
+  const PfspInstance& I = pfsp_instance_cached(inst, ub, gpu_branching(lb, br));
   Pool<PFSPNode> pool;
   pool.pushBack(pfsp_root());
   uint64_t tree = 0, sol = 0;
@@ -1457,9 +1490,9 @@ Result pfsp_gpu(int inst, const std::string& lb_str, int ub, int m, int M, int d
 }
 
 Result pfsp_gpu_rooted(int inst, const std::string& lb_str, int ub, int M, int device,
-                       unsigned long long capacity) {
+                       unsigned long long capacity, const std::string& br) {
   const LbKind lb = lb_from_string(lb_str);
-  const PfspInstance& I = pfsp_instance_cached(inst, ub);
+  const PfspInstance& I = pfsp_instance_cached(inst, ub, gpu_branching(lb, br));
   Result r;
   Pool<PFSPNode> pool;
   pool.pushBack(pfsp_root());
@@ -1512,9 +1545,11 @@ Result nqueens_gpu_rooted(int N, int g, int M, int device, unsigned long long ca
 
 Result pfsp_gpu_from_pool(const std::vector<PFSPNode>& nodes, int inst,
                           const std::string& lb_str, int ub, int best0, int m, int M,
-                          int device, const std::string& mode, unsigned long long capacity) {
+                          int device, const std::string& mode, unsigned long long capacity,
+                          const std::string& br) {
   const LbKind lb = lb_from_string(lb_str);
-  const PfspInstance& I = pfsp_instance_cached(inst, ub);
+  const PfspInstance& I = pfsp_instance_cached(inst, ub, gpu_branching(lb, br));
+  check_pfsp_pool(nodes.data(), nodes.size(), I.br);  // before any HIP call
   Pool<PFSPNode> pool;
   pool.pushBackBulk(nodes.data(), nodes.size());
   const int best = (best0 > 0) ? best0 : I.init_ub;
@@ -1585,6 +1620,9 @@ std::vector<NQNode> nq_gpu_frontier(int N, int g, size_t target, int device,
 std::vector<PFSPNode> pfsp_gpu_frontier(const PfspInstance& I, int lbk, size_t target,
                                         int device, int best0, uint64_t& tree,
                                         uint64_t& sol, int& best_out) {
+  if (I.br != Branching::FWD && lbk != 0)
+    throw std::invalid_argument(std::string("branching rule '") + branching_name(I.br) +
+                                "' on the gpu tier needs lb1_d");
   set_device_cached(device);
   const PfspDevTables& tb = pfsp_tables_cached(I, device);
   StreamGuard stream;
@@ -1619,7 +1657,7 @@ std::vector<PFSPNode> pfsp_gpu_frontier(const PfspInstance& I, int lbk, size_t t
     const unsigned long long Mi =
         std::min<unsigned long long>(M, std::max<unsigned long long>(bound, 1));
     enqueue_pfsp_iter(bufs, ctl_d.p + parity, ctl_d.p + (1 - parity), jobs, machines, lbg, tb,
-                      1, Mi, presum, stream.s);
+                      1, Mi, presum, stream.s, static_cast<int>(I.br));
   };
   DevLoopCfg cfg;
   cfg.m = 1;
@@ -1711,8 +1749,11 @@ void validate_nq_step(const std::vector<NQNode>& nodes, int N, int g, int finish
 
 void validate_pfsp_step(const std::vector<PFSPNode>& nodes, int inst, const std::string& lb,
                         unsigned long long m, unsigned long long M,
-                        unsigned long long capacity, int geom, const std::string& presum) {
+                        unsigned long long capacity, int geom, const std::string& presum,
+                        const std::string& br_str) {
   const LbKind lbk = lb_from_string(lb);
+  const Branching br = branching_from_string(br_str);
+  check_branching_supported(lbk, br, true);
   const int jobs = taillard_nb_jobs(inst);
   if (jobs > MAX_JOBS)
     throw std::invalid_argument("instance exceeds MAX_JOBS=20 (use ta001..ta030)");
@@ -1726,8 +1767,17 @@ void validate_pfsp_step(const std::vector<PFSPNode>& nodes, int inst, const std:
     const PFSPNode& p = nodes[i];
     if (p.depth < 0 || p.depth > jobs - 1)
       throw std::invalid_argument("node " + std::to_string(i) + ": depth not in 0..jobs-1");
-    if (p.limit1 != p.depth - 1)
-      throw std::invalid_argument("node " + std::to_string(i) + ": limit1 != depth - 1");
+    if (br == Branching::FWD) {
+      // the forward kernels take limit2 == jobs for granted
+      if (p.limit1 != p.depth - 1)
+        throw std::invalid_argument("node " + std::to_string(i) + ": limit1 != depth - 1");
+      if (p.nback != 0)
+        throw std::invalid_argument("node " + std::to_string(i) +
+                                    ": nback != 0 needs a non-fwd branching rule");
+    } else if (p.limit1 < -1 || p.limit1 + 1 + static_cast<int>(p.nback) != p.depth) {
+      throw std::invalid_argument("node " + std::to_string(i) +
+                                  ": depth != limit1 + 1 + nback");
+    }
     uint32_t seen = 0;
     for (int j = 0; j < jobs; j++) {
       if (p.prmu[j] >= jobs || (seen >> p.prmu[j] & 1u))
@@ -1777,10 +1827,11 @@ DevpoolStepCtl nq_devpool_step(std::vector<NQNode>& nodes, int N, int g, int fin
 DevpoolStepCtl pfsp_devpool_step(std::vector<PFSPNode>& nodes, int inst, const std::string& lb,
                                  int best, unsigned long long m, unsigned long long M,
                                  unsigned long long capacity, int geom,
-                                 const std::string& presum, int device) {
-  validate_pfsp_step(nodes, inst, lb, m, M, capacity, geom, presum);  // before any HIP call
+                                 const std::string& presum, int device,
+                                 const std::string& br) {
+  validate_pfsp_step(nodes, inst, lb, m, M, capacity, geom, presum, br);  // before any HIP call
   const int pm = presum_mode(presum);
-  const PfspInstance& I = pfsp_instance_cached(inst, 1);
+  const PfspInstance& I = pfsp_instance_cached(inst, 1, branching_from_string(br));
   const int jobs = I.jobs, machines = I.machines;
   const int lbg = geom < 0 ? devpool_lbk_geom(lbk_of(lb_from_string(lb)), machines) : geom;
   const size_t n = nodes.size();
@@ -1809,7 +1860,8 @@ DevpoolStepCtl pfsp_devpool_step(std::vector<PFSPNode>& nodes, int inst, const s
   HIP_CHECK(hipMemcpyAsync(ctl_d.p, &ctl, sizeof(DevCtl), hipMemcpyHostToDevice, stream.s));
   HIP_CHECK(hipMemcpyAsync(ctl_d.p + 1, &ctl, sizeof(DevCtl), hipMemcpyHostToDevice, stream.s));
   HIP_CHECK(hipStreamSynchronize(stream.s));
-  enqueue_pfsp_iter(bufs, ctl_d.p, ctl_d.p + 1, jobs, machines, lbg, tb, m, Mi, ps, stream.s);
+  enqueue_pfsp_iter(bufs, ctl_d.p, ctl_d.p + 1, jobs, machines, lbg, tb, m, Mi, ps, stream.s,
+                    static_cast<int>(I.br));
   HIP_CHECK(hipGetLastError());
   return step_readback(nodes, pool_d.p, ctl_d.p + 1, capacity, stream.s);
 }
@@ -1944,11 +1996,12 @@ std::vector<DevpoolSnapshot<NQNode>> nq_devpool_chain(
 std::vector<DevpoolSnapshot<PFSPNode>> pfsp_devpool_chain(
     const std::vector<PFSPNode>& nodes, int inst, const std::string& lb, int best,
     unsigned long long m, const std::vector<unsigned long long>& windows,
-    unsigned long long capacity, int geom, const std::string& presum, int device) {
-  validate_pfsp_step(nodes, inst, lb, m, 1, capacity, geom, presum);  // before any HIP call
+    unsigned long long capacity, int geom, const std::string& presum, int device,
+    const std::string& br) {
+  validate_pfsp_step(nodes, inst, lb, m, 1, capacity, geom, presum, br);  // before any HIP call
   validate_chain_windows(windows, taillard_nb_jobs(inst), capacity);
   const int pm = presum_mode(presum);
-  const PfspInstance& I = pfsp_instance_cached(inst, 1);
+  const PfspInstance& I = pfsp_instance_cached(inst, 1, branching_from_string(br));
   const int jobs = I.jobs, machines = I.machines;
   const int lbg = geom < 0 ? devpool_lbk_geom(lbk_of(lb_from_string(lb)), machines) : geom;
   const unsigned long long Mc = *std::max_element(windows.begin(), windows.end());
@@ -1973,7 +2026,7 @@ std::vector<DevpoolSnapshot<PFSPNode>> pfsp_devpool_chain(
                          devpool_iter_policy(Mc, windows[i], jobs, lbg, presum_alloc);
                      const bool ps = pm < 0 ? it.ps : pm == 1;
                      enqueue_pfsp_iter(bufs, cur, next, jobs, machines, lbg, tb, m, it.Mi, ps,
-                                       stream.s);
+                                       stream.s, static_cast<int>(I.br));
                    });
 }
 
@@ -2016,6 +2069,41 @@ std::vector<int32_t> pfsp_gpu_bounds(int inst, const std::string& lb_str,
 }
 
 
+std::pair<std::vector<int32_t>, std::vector<int32_t>> pfsp_gpu_bounds_bi(
+    int inst, const std::vector<PFSPNode>& nodes, int device) {
+  PfspInstance I = make_pfsp_instance(inst, 1);
+  // the kernel indexes prmu by [limit1 + 1, jobs - nback): check before any HIP call
+  for (size_t i = 0; i < nodes.size(); i++) {
+    const PFSPNode& p = nodes[i];
+    if (p.limit1 < -1 || p.limit1 + 1 + static_cast<int>(p.nback) > I.jobs)
+      throw std::invalid_argument("node " + std::to_string(i) +
+                                  ": limit1 + 1 + nback exceeds jobs");
+    for (int j = 0; j < I.jobs; j++)
+      if (p.prmu[j] >= I.jobs)
+        throw std::invalid_argument("node " + std::to_string(i) + ": prmu entry >= jobs");
+  }
+  set_device_cached(device);
+  PfspTablesGuard tables(I);
+  const size_t n = nodes.size();
+  std::vector<int32_t> lb_begin(n * I.jobs, -1), lb_end(n * I.jobs, -1);
+  if (n == 0) return {lb_begin, lb_end};
+  DevGuard<PFSPNode> parents_d(n);
+  DevGuard<int32_t> begin_d(n * I.jobs), end_d(n * I.jobs);
+  HIP_CHECK(hipMemcpy(parents_d.p, nodes.data(), n * sizeof(PFSPNode), hipMemcpyHostToDevice));
+  HIP_CHECK(hipMemset(begin_d.p, 255, n * I.jobs * sizeof(int32_t)));
+  HIP_CHECK(hipMemset(end_d.p, 255, n * I.jobs * sizeof(int32_t)));
+  (void)hipGetLastError();  // drop a stale launch error of an earlier, unchecked call
+  launch_pfsp_eval(parents_d.p, static_cast<int>(n), I.jobs, I.machines, 0, tables.tb, 0,
+                   begin_d.p, nullptr, static_cast<int>(Branching::MINBRANCH), end_d.p);
+  HIP_CHECK(hipGetLastError());
+  HIP_CHECK(hipMemcpy(lb_begin.data(), begin_d.p, n * I.jobs * sizeof(int32_t),
+                      hipMemcpyDeviceToHost));
+  HIP_CHECK(hipMemcpy(lb_end.data(), end_d.p, n * I.jobs * sizeof(int32_t),
+                      hipMemcpyDeviceToHost));
+  return {lb_begin, lb_end};
+}
+
+
 // ---------------------------------------------------------------------------
 // Asynchronous PFSP engine: runs the devpool search on a background thread
 // and exposes a shared incumbent, so the Python distributed tier can run a
@@ -2026,9 +2114,13 @@ std::vector<int32_t> pfsp_gpu_bounds(int inst, const std::string& lb_str,
 // ---------------------------------------------------------------------------
 
 PfspAsyncEngine::PfspAsyncEngine(int inst, const std::string& lb_str, int ub, int m,
-                                 int M, int device, unsigned long long capacity)
+                                 int M, int device, unsigned long long capacity,
+                                 const std::string& br)
     : inst_(inst), ub_(ub), m_(m), M_(M), device_(device), lb_(lb_str),
       capacity_(capacity), shared_best_(0) {
+  if (branching_from_string(br) != Branching::FWD)
+    throw std::invalid_argument("branching rule '" + br +
+                                "' is not yet supported by PfspAsyncEngine (fwd only)");
   const PfspInstance& I = pfsp_instance_cached(inst, ub);
   shared_best_.store(I.init_ub);
   result_.optimum = I.init_ub;
@@ -2037,8 +2129,9 @@ PfspAsyncEngine::PfspAsyncEngine(int inst, const std::string& lb_str, int ub, in
 
 PfspAsyncEngine::PfspAsyncEngine(std::vector<PFSPNode> nodes, int inst,
                                  const std::string& lb_str, int ub, int best0, int m, int M,
-                                 int device, unsigned long long capacity)
-    : PfspAsyncEngine(inst, lb_str, ub, m, M, device, capacity) {
+                                 int device, unsigned long long capacity,
+                                 const std::string& br)
+    : PfspAsyncEngine(inst, lb_str, ub, m, M, device, capacity, br) {
   submit(std::move(nodes), best0);
 }
 

@@ -86,8 +86,13 @@ Result nqueens_gpu_from_pool(const std::vector<NQNode>& nodes, int N, int g, int
                              int device, const std::string& mode,
                              unsigned long long capacity);
 
+// br (all PFSP single-GPU entry points): branching rule "fwd" (default, the
+// reference's tree), "bwd", "alt" or "minbranch" (search_host.hpp). Non-fwd
+// rules run the both-directions lb1_d kernels and need lb == "lb1_d"; any
+// other combination throws std::invalid_argument.
 Result pfsp_gpu(int inst, const std::string& lb, int ub, int m, int M, int device,
-                const std::string& mode, unsigned long long capacity);
+                const std::string& mode, unsigned long long capacity,
+                const std::string& br = "fwd");
 // Device-rooted search: the WHOLE search runs in the devpool from the root
 // (no CPU phase-1 BFS, no host frontier marshaling, no CPU phase 3) — the
 // devpool's m is 1 so the pool drains on device. One slice thread starts at
@@ -97,11 +102,12 @@ Result pfsp_gpu(int inst, const std::string& lb, int ub, int m, int M, int devic
 // Counts equal the sequential engine's at ub=1 (pruning is
 // decomposition-invariant); the phase split is all-phase-2 by construction.
 Result pfsp_gpu_rooted(int inst, const std::string& lb, int ub, int M, int device,
-                       unsigned long long capacity);
+                       unsigned long long capacity, const std::string& br = "fwd");
 Result nqueens_gpu_rooted(int N, int g, int M, int device, unsigned long long capacity);
 Result pfsp_gpu_from_pool(const std::vector<PFSPNode>& nodes, int inst, const std::string& lb,
                           int ub, int best0, int m, int M, int device,
-                          const std::string& mode, unsigned long long capacity);
+                          const std::string& mode, unsigned long long capacity,
+                          const std::string& br = "fwd");
 
 // engine_multi.cpp: in-process multi-GPU tier (eval = "devpool", "gpu" or
 // "cpu"; capacity is the per-slice-thread device pool size in nodes, devpool
@@ -110,7 +116,8 @@ Result nqueens_multigpu(int N, int g, int m, int M, int D, const std::string& ev
                         double perc = 0.5, unsigned long long capacity = 1ull << 27);
 Result pfsp_multigpu(int inst, const std::string& lb, int ub, int m, int M, int D,
                      const std::string& eval, bool share_best, double perc = 0.5,
-                     unsigned long long capacity = 1ull << 27);
+                     unsigned long long capacity = 1ull << 27,
+                     const std::string& br = "fwd");  // non-fwd rules: not yet, throws
 
 // Persistent per-rank PFSP engine: a background thread that accepts
 // successive frontiers (submit), runs the devpool search on each, exposes a
@@ -122,11 +129,13 @@ Result pfsp_multigpu(int inst, const std::string& lb, int ub, int m, int M, int 
 // frontier claims pay no re-arm cost.
 class PfspAsyncEngine {
  public:
+  // br: only "fwd" is supported yet; any other rule throws
   PfspAsyncEngine(int inst, const std::string& lb, int ub, int m, int M, int device,
-                  unsigned long long capacity);
+                  unsigned long long capacity, const std::string& br = "fwd");
   // one-shot convenience (round-1 API): submits `nodes` immediately
   PfspAsyncEngine(std::vector<PFSPNode> nodes, int inst, const std::string& lb, int ub,
-                  int best0, int m, int M, int device, unsigned long long capacity);
+                  int best0, int m, int M, int device, unsigned long long capacity,
+                  const std::string& br = "fwd");
   ~PfspAsyncEngine();
   void submit(std::vector<PFSPNode> nodes, int best0);
   int best() const;
@@ -192,7 +201,8 @@ void validate_nq_step(const std::vector<NQNode>& nodes, int N, int g, int finish
                       unsigned long long capacity, const std::string& presum);
 void validate_pfsp_step(const std::vector<PFSPNode>& nodes, int inst, const std::string& lb,
                         unsigned long long m, unsigned long long M,
-                        unsigned long long capacity, int geom, const std::string& presum);
+                        unsigned long long capacity, int geom, const std::string& presum,
+                        const std::string& br = "fwd");
 DevpoolStepCtl nq_devpool_step(std::vector<NQNode>& nodes, int N, int g, int finish,
                                unsigned long long m, unsigned long long M,
                                unsigned long long capacity, const std::string& presum,
@@ -200,7 +210,8 @@ DevpoolStepCtl nq_devpool_step(std::vector<NQNode>& nodes, int N, int g, int fin
 DevpoolStepCtl pfsp_devpool_step(std::vector<PFSPNode>& nodes, int inst, const std::string& lb,
                                  int best, unsigned long long m, unsigned long long M,
                                  unsigned long long capacity, int geom,
-                                 const std::string& presum, int device);
+                                 const std::string& presum, int device,
+                                 const std::string& br = "fwd");
 
 // Chain entry points (kernel-level tests): the step functions' arguments and
 // validation, with `windows` (1..16 per-iteration launch windows) in place of
@@ -231,12 +242,18 @@ std::vector<DevpoolSnapshot<NQNode>> nq_devpool_chain(
 std::vector<DevpoolSnapshot<PFSPNode>> pfsp_devpool_chain(
     const std::vector<PFSPNode>& nodes, int inst, const std::string& lb, int best,
     unsigned long long m, const std::vector<unsigned long long>& windows,
-    unsigned long long capacity, int geom, const std::string& presum, int device);
+    unsigned long long capacity, int geom, const std::string& presum, int device,
+    const std::string& br = "fwd");
 
 std::vector<uint8_t> nq_gpu_labels(int N, int g, const std::vector<NQNode>& nodes,
                                    int device);
 std::vector<int32_t> pfsp_gpu_bounds(int inst, const std::string& lb,
                                      const std::vector<PFSPNode>& nodes, int best,
                                      int device);
+// lb1_d child bounds in both directions, [n * jobs] each, indexed by position
+// (-1 outside a parent's unscheduled range): first = children fixed at the
+// front (lb_begin), second = children fixed at the back (lb_end).
+std::pair<std::vector<int32_t>, std::vector<int32_t>> pfsp_gpu_bounds_bi(
+    int inst, const std::vector<PFSPNode>& nodes, int device);
 
 }  // namespace gats

@@ -219,6 +219,8 @@ struct PfspGpuCtx {
     tb.johnson_packed_w = upload_n(pk.jp_w.data(), pk.jp_w.size());
     tb.pairs1_w = upload_n(pk.p1_w.data(), pk.p1_w.size());
     tb.pairs2_w = upload_n(pk.p2_w.data(), pk.p2_w.size());
+    std::vector<int32_t> mh(I.lb1.min_heads.begin(), I.lb1.min_heads.end());
+    tb.min_heads = upload(mh);
   }
   ~PfspGpuCtx() {
     (void)hipStreamDestroy(stream);
@@ -426,7 +428,10 @@ Result nqueens_multigpu(int N, int g, int m, int M, int D, const std::string& ev
 
 Result pfsp_multigpu(int inst, const std::string& lb_str, int ub, int m, int M, int D,
                      const std::string& eval, bool share_best, double perc,
-                     unsigned long long capacity) {
+                     unsigned long long capacity, const std::string& br) {
+  if (branching_from_string(br) != Branching::FWD)
+    throw std::invalid_argument("branching rule '" + br +
+                                "' is not yet supported on the multigpu tier (fwd only)");
   if (D < 1) throw std::invalid_argument("D must be >= 1");
   if (!(perc > 0.0 && perc < 1.0))
     throw std::invalid_argument("perc must be in (0,1) (reference: 0 < --perc < 100)");

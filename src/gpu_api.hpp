@@ -51,6 +51,9 @@ struct PfspDevTables {
   const uint32_t* johnson_packed_w;  // [pairs * jobs]
   const uint8_t* pairs1_w;           // [pairs]
   const uint8_t* pairs2_w;           // [pairs]
+  // front schedule of a node with nothing fixed at the front (limit1 == -1
+  // with jobs fixed at the back: backward / dynamic branching only)
+  const int32_t* min_heads;          // [machines]
 };
 
 
@@ -60,8 +63,13 @@ struct PfspDevTables {
 void launch_nq_eval(const NQNode* parents, int n, int N, int g, uint8_t* labels,
                     hipStream_t s);
 // lbk: 0 = lb1_d, 1 = lb1, 2 = lb2
+// br: branching rule code (0 fwd, 1 bwd, 2 alt, 3 minbranch = the Branching
+// enum). br == 0 launches the forward kernels; br != 0 requires lbk == 0 and
+// launches the both-directions lb1_d kernel, which fills `bounds` (front
+// children) and `bounds_end` (back children), both [n * jobs] by position.
 void launch_pfsp_eval(const PFSPNode* parents, int n, int jobs, int machines, int lbk,
-                      const PfspDevTables& tb, int best, int32_t* bounds, hipStream_t s);
+                      const PfspDevTables& tb, int best, int32_t* bounds, hipStream_t s,
+                      int br = 0, int32_t* bounds_end = nullptr);
 
 // devpool v3 (see kernels.hip): expand -> scan -> gather, 3 kernels/iteration.
 // lbk geometry codes: 0 lb1_d, 1 thread-per-child, 2 wave-coop lb2,
@@ -76,7 +84,7 @@ void launch_nq_x(const DevCtl* ctl, const NQNode* pool, NQNode* childbuf,
 void launch_pfsp_x(DevCtl* ctl, const PFSPNode* pool, PFSPNode* childbuf, uint32_t* bc,
                    unsigned long long* bs, int jobs, int machines, int lbk,
                    const PfspDevTables& tb, unsigned long long m, unsigned long long M,
-                   hipStream_t s);
+                   hipStream_t s, int br = 0);
 void launch_gather2_nq(const DevCtl* ctl_cur, DevCtl* ctl_next, const uint32_t* bc,
                        const unsigned long long* bs, const unsigned long long* be,
                        const uint32_t* groupSums, const NQNode* childbuf, NQNode* pool,

@@ -25,6 +25,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdlib>
+#include <stdexcept>
 #include <type_traits>
 
 #include "gpu_api.hpp"
@@ -91,6 +92,44 @@ __device__ inline void emit_pfsp_child(PFSPNode* pool, unsigned long long slot,
   uint8_t* db = reinterpret_cast<uint8_t*>(d);
   db[2 + depth] = parent.prmu[k];
   db[2 + k] = parent.prmu[depth];
+}
+
+// Children of a node that may have jobs fixed at the back (nback > 0,
+// backward / dynamic branching). The forward child fixes prmu[k] at position
+// limit1 + 1 (== depth only while nback == 0, which is why emit_pfsp_child
+// cannot be reused): bytes 0, 1 and the two swapped prmu bytes change.
+__device__ inline void emit_pfsp_child_front(PFSPNode* pool, unsigned long long slot,
+                                             const PFSPNode& parent, int depth, int limit1,
+                                             int k) {
+  const unsigned long long* s = reinterpret_cast<const unsigned long long*>(&parent);
+  unsigned long long* d = reinterpret_cast<unsigned long long*>(&pool[slot]);
+  d[0] = (s[0] & ~0xFFFFull) |
+         static_cast<unsigned long long>(static_cast<uint8_t>(depth + 1)) |
+         (static_cast<unsigned long long>(static_cast<uint8_t>(limit1 + 1)) << 8);
+  d[1] = s[1];
+  d[2] = s[2];
+  uint8_t* db = reinterpret_cast<uint8_t*>(d);
+  const int pos = limit1 + 1;
+  db[2 + pos] = parent.prmu[k];
+  db[2 + k] = parent.prmu[pos];
+}
+
+// The backward child fixes prmu[k] at position limit2 - 1 = jobs - nback - 1:
+// byte 0 (depth), byte 22 (nback) and the two swapped prmu bytes change.
+__device__ inline void emit_pfsp_child_back(PFSPNode* pool, unsigned long long slot,
+                                            const PFSPNode& parent, int depth, int nback,
+                                            int jobs, int k) {
+  const unsigned long long* s = reinterpret_cast<const unsigned long long*>(&parent);
+  unsigned long long* d = reinterpret_cast<unsigned long long*>(&pool[slot]);
+  d[0] = (s[0] & ~0xFFull) | static_cast<unsigned long long>(static_cast<uint8_t>(depth + 1));
+  d[1] = s[1];
+  // byte 22 is bits 48..55 of the third qword
+  d[2] = (s[2] & ~(0xFFull << 48)) |
+         (static_cast<unsigned long long>(static_cast<uint8_t>(nback + 1)) << 48);
+  uint8_t* db = reinterpret_cast<uint8_t*>(d);
+  const int pos = jobs - nback - 1;
+  db[2 + pos] = parent.prmu[k];
+  db[2 + k] = parent.prmu[pos];
 }
 
 // ---------------------------------------------------------------------------
@@ -290,6 +329,101 @@ __device__ inline int lb1d_child_bound(const LdsLb1<MM>& lds, const int* front,
   return lb;
 }
 
+// ---- lb1_d in both directions (backward / dynamic branching) ----
+
+template <int MM>
+struct LdsLb1Bi {
+  int16_t p[MM * MAX_JOBS];
+  int32_t min_tails[MM];
+  int32_t min_heads[MM];
+};
+
+template <int MM>
+__device__ inline void stage_lb1bi_tables(LdsLb1Bi<MM>& lds, const PfspDevTables& tb,
+                                          int jobs) {
+  stage_lb1_tables<MM>(lds, tb, jobs);
+  if (threadIdx.x < MM) lds.min_heads[threadIdx.x] = tb.min_heads[threadIdx.x];
+}
+
+// Parent state shared by all of its children in both directions
+// (c_bound_simple.c:52-124): front = schedule_front (min_heads when nothing is
+// fixed at the front), back = schedule_back (min_tails when nothing is fixed
+// at the back), remain = work of the unscheduled positions [limit1+1, limit2).
+// Three register arrays, every machine index compile-time.
+template <int MM>
+__device__ inline void lb1d_bi_setup(const LdsLb1Bi<MM>& lds, const uint8_t* prmu, int limit1,
+                                     int limit2, int jobs, int* front, int* back,
+                                     int* remain) {
+#pragma unroll
+  for (int i = 0; i < MM; i++) front[i] = back[i] = remain[i] = 0;
+  if (limit1 == -1) {
+#pragma unroll
+    for (int i = 0; i < MM; i++) front[i] = lds.min_heads[i];
+  } else {
+    for (int i = 0; i <= limit1; i++) {
+      const int job = prmu[i];
+      front[0] += lds.p[job];
+#pragma unroll
+      for (int j = 1; j < MM; j++)
+        front[j] = max(front[j - 1], front[j]) + lds.p[j * jobs + job];
+    }
+  }
+  if (limit2 == jobs) {
+#pragma unroll
+    for (int i = 0; i < MM; i++) back[i] = lds.min_tails[i];
+  } else {
+    for (int k = jobs - 1; k >= limit2; k--) {
+      const int job = prmu[k];
+      back[MM - 1] += lds.p[(MM - 1) * jobs + job];
+#pragma unroll
+      for (int jj = 0; jj < MM - 1; jj++) {
+        constexpr int last = MM - 2;
+        const int j = last - jj;  // MM-2 .. 0, compile-time after unrolling
+        back[j] = max(back[j], back[j + 1]) + lds.p[j * jobs + job];
+      }
+    }
+  }
+  for (int i = limit1 + 1; i < limit2; i++) {
+    const int job = prmu[i];
+#pragma unroll
+    for (int j = 0; j < MM; j++) remain[j] += lds.p[j * jobs + job];
+  }
+}
+
+// add_front_and_bound with a general back schedule (c_bound_simple.c:218-244).
+template <int MM>
+__device__ inline int lb1d_bound_front(const LdsLb1Bi<MM>& lds, const int* front,
+                                       const int* back, const int* remain, int job,
+                                       int jobs) {
+  int lb = front[0] + remain[0] + back[0];
+  int tmp0 = front[0] + lds.p[job];
+#pragma unroll
+  for (int j = 1; j < MM; j++) {
+    const int tmp1 = max(tmp0, front[j]);
+    lb = max(lb, tmp1 + remain[j] + back[j]);
+    tmp0 = tmp1 + lds.p[j * jobs + job];
+  }
+  return lb;
+}
+
+// add_back_and_bound (c_bound_simple.c:246-275): the mirror image — machines
+// in descending order, front and back swap roles.
+template <int MM>
+__device__ inline int lb1d_bound_back(const LdsLb1Bi<MM>& lds, const int* front,
+                                      const int* back, const int* remain, int job,
+                                      int jobs) {
+  int lb = front[MM - 1] + remain[MM - 1] + back[MM - 1];
+  int tmp0 = back[MM - 1] + lds.p[(MM - 1) * jobs + job];
+#pragma unroll
+  for (int jj = 0; jj < MM - 1; jj++) {
+    const int j = MM - 2 - jj;  // MM-2 .. 0
+    const int tmp1 = max(tmp0, back[j]);
+    lb = max(lb, tmp1 + remain[j] + front[j]);
+    tmp0 = tmp1 + lds.p[j * jobs + job];
+  }
+  return lb;
+}
+
 // lb2: Johnson two-machine relaxation over all machine pairs with early exit
 // (c_bound_johnson.c:211-254). Pair order is identity (LB2_FULL). `front` is
 // this thread's LDS slice (runtime-indexed by pair machine ids).
@@ -409,6 +543,31 @@ __global__ void k_pfsp_eval_lb1d(const PFSPNode* parents, int n, int jobs, PfspD
   lb1d_setup<MM>(lds, parent.prmu, parent.limit1, jobs, front, remain);
   for (int k = parent.limit1 + 1; k < jobs; k++)
     bounds[t * jobs + k] = lb1d_child_bound<MM>(lds, front, remain, parent.prmu[k], jobs);
+}
+
+// lb1_d in both directions, one thread per parent: lb_begin / lb_end per
+// unscheduled POSITION; the host chooses the direction (hostpool, non-fwd
+// branching rules).
+template <int MM>
+__global__ void k_pfsp_eval_lb1d_bi(const PFSPNode* parents, int n, int jobs,
+                                    PfspDevTables tb, int32_t* lb_begin, int32_t* lb_end) {
+  __shared__ LdsLb1Bi<MM> lds;
+  __shared__ PFSPNode snodes[BLOCK];
+  stage_lb1bi_tables<MM>(lds, tb, jobs);
+  const unsigned long long t =
+      static_cast<unsigned long long>(blockIdx.x) * blockDim.x + threadIdx.x;
+  const int lp = stage_parents(parents, static_cast<unsigned long long>(n), 1, snodes, t);
+  __syncthreads();
+  if (lp < 0) return;
+  const PFSPNode& parent = snodes[lp];
+  const int limit1 = parent.limit1, limit2 = jobs - parent.nback;
+  int front[MM], back[MM], remain[MM];
+  lb1d_bi_setup<MM>(lds, parent.prmu, limit1, limit2, jobs, front, back, remain);
+  for (int k = limit1 + 1; k < limit2; k++) {
+    const int job = parent.prmu[k];
+    lb_begin[t * jobs + k] = lb1d_bound_front<MM>(lds, front, back, remain, job, jobs);
+    lb_end[t * jobs + k] = lb1d_bound_back<MM>(lds, front, back, remain, job, jobs);
+  }
 }
 
 template <int MM>
@@ -797,6 +956,94 @@ __global__ void k_pfsp_x_lb1d(DevCtl* ctl, const PFSPNode* pool, PFSPNode* child
   }
 }
 
+// K1 for PFSP lb1_d under a non-forward branching rule (br: 1 bwd, 2 alt,
+// 3 minbranch): same contract and geometry as k_pfsp_x_lb1d — one thread per
+// parent, survivors compacted into the block's BLOCK*MAX_JOBS slab, per-block
+// counts out, atomicMin on ctl->best at leaves only. Each thread builds the
+// parent's front / back / remain once, pass 1 evaluates the O(m) child bounds
+// (both directions for minbranch, only the rule's direction otherwise) and
+// accumulates the survivor counts and bound sums, the direction is decided,
+// and pass 2 recomputes the chosen direction's bounds and emits (recompute,
+// not store: a job-indexed local array would spill to scratch).
+template <int MM>
+__global__ void k_pfsp_x_lb1d_bi(DevCtl* ctl, const PFSPNode* pool, PFSPNode* childbuf,
+                                 uint32_t* blockCounts, unsigned long long* blockSols,
+                                 int jobs, PfspDevTables tb, unsigned long long m,
+                                 unsigned long long M, int br) {
+  __shared__ LdsLb1Bi<MM> lds;
+  __shared__ PFSPNode s[BLOCK];
+  stage_lb1bi_tables<MM>(lds, tb, jobs);
+  const unsigned long long c = derive_chunk(ctl, m, M);
+  const PFSPNode* parents = pool + (ctl->size - c);
+  const unsigned long long t =
+      static_cast<unsigned long long>(blockIdx.x) * blockDim.x + threadIdx.x;
+  const int lp = stage_parents(parents, c, 1, s, t);
+  __syncthreads();
+  const int best = ctl->best;
+
+  int front[MM], back[MM], remain[MM];
+  uint32_t cnt = 0;
+  unsigned long long sols = 0;
+  int depth = 0, limit1 = 0, limit2 = 0;
+  bool bwd = false;
+  if (lp >= 0) {
+    const PFSPNode& p = s[lp];
+    depth = p.depth;
+    limit1 = p.limit1;
+    limit2 = jobs - p.nback;
+    lb1d_bi_setup<MM>(lds, p.prmu, limit1, limit2, jobs, front, back, remain);
+    const bool dyn = br == 3;
+    bwd = br == 1 || (br == 2 && (depth & 1));
+    int cntF = 0, cntB = 0, sumF = 0, sumB = 0;
+    int minF = 0x7fffffff, minB = 0x7fffffff;
+    for (int k = limit1 + 1; k < limit2; k++) {
+      const int job = s[lp].prmu[k];
+      if (dyn || !bwd) {
+        const int lb = lb1d_bound_front<MM>(lds, front, back, remain, job, jobs);
+        cntF += lb < best;
+        sumF += lb;
+        minF = min(minF, lb);
+      }
+      if (dyn || bwd) {
+        const int lb = lb1d_bound_back<MM>(lds, front, back, remain, job, jobs);
+        cntB += lb < best;
+        sumB += lb;
+        minB = min(minB, lb);
+      }
+    }
+    if (dyn) bwd = cntB < cntF || (cntB == cntF && sumB > sumF);
+    if (depth + 1 == jobs) {
+      sols = static_cast<unsigned long long>(limit2 - (limit1 + 1));
+      const int lb = bwd ? minB : minF;
+      if (limit2 > limit1 + 1 && lb < best) atomicMin(&ctl->best, lb);
+    } else {
+      cnt = static_cast<uint32_t>(bwd ? cntB : cntF);
+    }
+  }
+  uint32_t totC;
+  const uint32_t pre = block_excl_scan(cnt, totC);
+  const unsigned long long totS = block_reduce_u64(sols);
+  if (threadIdx.x == 0) {
+    blockCounts[blockIdx.x] = totC;
+    blockSols[blockIdx.x] = totS;
+  }
+  if (cnt > 0) {
+    unsigned long long slot =
+        static_cast<unsigned long long>(blockIdx.x) * (BLOCK * MAX_JOBS) + pre;
+    const int nback = jobs - limit2;
+    for (int k = limit1 + 1; k < limit2; k++) {
+      const int job = s[lp].prmu[k];
+      if (bwd) {
+        if (lb1d_bound_back<MM>(lds, front, back, remain, job, jobs) < best)
+          emit_pfsp_child_back(childbuf, slot++, s[lp], depth, nback, jobs, k);
+      } else {
+        if (lb1d_bound_front<MM>(lds, front, back, remain, job, jobs) < best)
+          emit_pfsp_child_front(childbuf, slot++, s[lp], depth, limit1, k);
+      }
+    }
+  }
+}
+
 
 
 // Wave-cooperative lb2 expand: phase A builds each child's front schedule and
@@ -1118,8 +1365,11 @@ void launch_nq_eval(const NQNode* parents, int n, int N, int g, uint8_t* labels,
 template <int MM>
 static void launch_pfsp_eval_mm(const PFSPNode* parents, int n, int jobs, int lbk,
                                 const PfspDevTables& tb, int best, int32_t* bounds,
-                                hipStream_t s) {
-  if (lbk == 0) {  // lb1_d: thread per parent
+                                hipStream_t s, int br, int32_t* bounds_end) {
+  if (br != 0) {  // lb1_d in both directions (launch_pfsp_eval rejects other bounds)
+    hipLaunchKernelGGL((k_pfsp_eval_lb1d_bi<MM>), dim3(grid_for(n)), dim3(BLOCK), 0, s,
+                       parents, n, jobs, tb, bounds, bounds_end);
+  } else if (lbk == 0) {  // lb1_d: thread per parent
     hipLaunchKernelGGL((k_pfsp_eval_lb1d<MM>), dim3(grid_for(n)), dim3(BLOCK), 0, s, parents,
                        n, jobs, tb, bounds);
   } else if (lbk == 1) {
@@ -1134,13 +1384,17 @@ static void launch_pfsp_eval_mm(const PFSPNode* parents, int n, int jobs, int lb
 }
 
 void launch_pfsp_eval(const PFSPNode* parents, int n, int jobs, int machines, int lbk,
-                      const PfspDevTables& tb, int best, int32_t* bounds, hipStream_t s) {
+                      const PfspDevTables& tb, int best, int32_t* bounds, hipStream_t s,
+                      int br, int32_t* bounds_end) {
+  if (br != 0 && (lbk != 0 || bounds_end == nullptr))
+    throw std::invalid_argument(
+        "launch_pfsp_eval: a non-fwd branching rule needs lb1_d and a bounds_end buffer");
   if (machines == 5)
-    launch_pfsp_eval_mm<5>(parents, n, jobs, lbk, tb, best, bounds, s);
+    launch_pfsp_eval_mm<5>(parents, n, jobs, lbk, tb, best, bounds, s, br, bounds_end);
   else if (machines == 10)
-    launch_pfsp_eval_mm<10>(parents, n, jobs, lbk, tb, best, bounds, s);
+    launch_pfsp_eval_mm<10>(parents, n, jobs, lbk, tb, best, bounds, s, br, bounds_end);
   else
-    launch_pfsp_eval_mm<20>(parents, n, jobs, lbk, tb, best, bounds, s);
+    launch_pfsp_eval_mm<20>(parents, n, jobs, lbk, tb, best, bounds, s, br, bounds_end);
 }
 
 // ---- devpool v3 launchers ----
@@ -1194,8 +1448,11 @@ template <int MM>
 static void launch_pfsp_x_mm(DevCtl* ctl, const PFSPNode* pool, PFSPNode* childbuf,
                              uint32_t* bc, unsigned long long* bs, int jobs, int lbk,
                              const PfspDevTables& tb, unsigned long long m,
-                             unsigned long long M, hipStream_t s) {
-  if (lbk == 0) {
+                             unsigned long long M, hipStream_t s, int br) {
+  if (br != 0) {  // lb1_d geometry (code 0), both-directions kernel
+    hipLaunchKernelGGL((k_pfsp_x_lb1d_bi<MM>), dim3(devpool_grid(M, jobs, 0)), dim3(BLOCK), 0,
+                       s, ctl, pool, childbuf, bc, bs, jobs, tb, m, M, br);
+  } else if (lbk == 0) {
     hipLaunchKernelGGL((k_pfsp_x_lb1d<MM>), dim3(devpool_grid(M, jobs, 0)), dim3(BLOCK), 0, s,
                        ctl, pool, childbuf, bc, bs, jobs, tb, m, M);
   } else if (lbk == 1) {
@@ -1215,13 +1472,15 @@ static void launch_pfsp_x_mm(DevCtl* ctl, const PFSPNode* pool, PFSPNode* childb
 void launch_pfsp_x(DevCtl* ctl, const PFSPNode* pool, PFSPNode* childbuf, uint32_t* bc,
                    unsigned long long* bs, int jobs, int machines, int lbk,
                    const PfspDevTables& tb,
-                   unsigned long long m, unsigned long long M, hipStream_t s) {
+                   unsigned long long m, unsigned long long M, hipStream_t s, int br) {
+  if (br != 0 && lbk != 0)
+    throw std::invalid_argument("launch_pfsp_x: a non-fwd branching rule needs lb1_d");
   if (machines == 5)
-    launch_pfsp_x_mm<5>(ctl, pool, childbuf, bc, bs, jobs, lbk, tb, m, M, s);
+    launch_pfsp_x_mm<5>(ctl, pool, childbuf, bc, bs, jobs, lbk, tb, m, M, s, br);
   else if (machines == 10)
-    launch_pfsp_x_mm<10>(ctl, pool, childbuf, bc, bs, jobs, lbk, tb, m, M, s);
+    launch_pfsp_x_mm<10>(ctl, pool, childbuf, bc, bs, jobs, lbk, tb, m, M, s, br);
   else
-    launch_pfsp_x_mm<20>(ctl, pool, childbuf, bc, bs, jobs, lbk, tb, m, M, s);
+    launch_pfsp_x_mm<20>(ctl, pool, childbuf, bc, bs, jobs, lbk, tb, m, M, s, br);
 }
 
 void launch_presum(const uint32_t* bc, uint32_t* groupSums, int G, hipStream_t s) {

@@ -25,11 +25,16 @@ struct alignas(4) NQNode {
 };
 static_assert(sizeof(NQNode) == 24, "NQNode must be 24 bytes");
 
+// nback = number of jobs fixed at the BACK of the permutation (backward /
+// dynamic branching, beyond the reference): limit2 = jobs - nback,
+// depth = (limit1 + 1) + nback, unscheduled positions limit1+1 .. limit2-1.
+// nback == 0 is the forward-only node of the reference.
 struct alignas(4) PFSPNode {
   int8_t depth;
   int8_t limit1;
   uint8_t prmu[MAX_JOBS];
-  uint8_t pad_[2];
+  uint8_t nback;
+  uint8_t pad_[1];
 };
 static_assert(sizeof(PFSPNode) == 24, "PFSPNode must be 24 bytes");
 

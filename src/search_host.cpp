@@ -23,6 +23,50 @@ LbKind lb_from_string(const std::string& s) {
   throw std::invalid_argument("unsupported lower bound '" + s + "' (lb1, lb1_d, lb2)");
 }
 
+Branching branching_from_string(const std::string& s) {
+  if (s == "fwd") return Branching::FWD;
+  if (s == "bwd") return Branching::BWD;
+  if (s == "alt") return Branching::ALT;
+  if (s == "minbranch") return Branching::MINBRANCH;
+  throw std::invalid_argument("unsupported branching rule '" + s +
+                              "' (fwd, bwd, alt, minbranch)");
+}
+
+const char* branching_name(Branching br) {
+  switch (br) {
+    case Branching::BWD:
+      return "bwd";
+    case Branching::ALT:
+      return "alt";
+    case Branching::MINBRANCH:
+      return "minbranch";
+    default:
+      return "fwd";
+  }
+}
+
+void check_branching_supported(LbKind lb, Branching br, bool gpu_tier) {
+  if (br == Branching::FWD) return;
+  const char* lbn = lb == LbKind::LB1 ? "lb1" : (lb == LbKind::LB1_D ? "lb1_d" : "lb2");
+  if (br == Branching::MINBRANCH && lb != LbKind::LB1_D)
+    throw std::invalid_argument(std::string("branching rule 'minbranch' with bound '") + lbn +
+                                "' is not supported: minbranch needs both directions' "
+                                "bounds of every child (lb1_d only)");
+  if (gpu_tier && lb != LbKind::LB1_D)
+    throw std::invalid_argument(std::string("branching rule '") + branching_name(br) +
+                                "' with bound '" + lbn +
+                                "' is not supported on the gpu tier: the bi-directional "
+                                "kernels exist for lb1_d only");
+}
+
+void check_pfsp_pool(const PFSPNode* nodes, size_t n, Branching br) {
+  if (br != Branching::FWD) return;
+  for (size_t i = 0; i < n; i++)
+    if (nodes[i].nback != 0)
+      throw std::invalid_argument("node " + std::to_string(i) +
+                                  ": nback != 0 needs a non-fwd branching rule (br)");
+}
+
 // ---------------- N-Queens ----------------
 
 bool nq_is_safe(const uint8_t* board, int depth, int row_pos, int g) {
@@ -163,10 +207,11 @@ void nq_generate_children(const NQNode* parents, size_t n, int N, const uint8_t*
 
 // ---------------- PFSP ----------------
 
-PfspInstance make_pfsp_instance(int inst, int ub) {
+PfspInstance make_pfsp_instance(int inst, int ub, Branching br) {
   if (ub != 0 && ub != 1) throw std::invalid_argument("ub must be 0 or 1");
   PfspInstance I;
   I.inst = inst;
+  I.br = br;
   I.jobs = taillard_nb_jobs(inst);
   I.machines = taillard_nb_machines(inst);
   if (I.jobs > MAX_JOBS)
@@ -238,10 +283,98 @@ void decompose_lb2(const PfspInstance& I, const PFSPNode& parent, uint64_t& tree
   }
 }
 
+// Children of a node that may already have jobs fixed at the back: the
+// forward child fixes prmu[i] at position limit1 + 1, the backward child at
+// position limit2 - 1 (limit2 = jobs - nback).
+inline PFSPNode make_child_front(const PFSPNode& parent, int i) {
+  PFSPNode child = parent;
+  const int pos = parent.limit1 + 1;
+  child.depth = static_cast<int8_t>(parent.depth + 1);
+  child.limit1 = static_cast<int8_t>(pos);
+  child.prmu[pos] = parent.prmu[i];
+  child.prmu[i] = parent.prmu[pos];
+  return child;
+}
+
+inline PFSPNode make_child_back(const PFSPNode& parent, int jobs, int i) {
+  PFSPNode child = parent;
+  const int pos = jobs - parent.nback - 1;
+  child.depth = static_cast<int8_t>(parent.depth + 1);
+  child.nback = static_cast<uint8_t>(parent.nback + 1);
+  child.prmu[pos] = parent.prmu[i];
+  child.prmu[i] = parent.prmu[pos];
+  return child;
+}
+
+// Direction of a parent's children under a static rule.
+inline bool static_backward(Branching br, int depth) {
+  return br == Branching::BWD || (br == Branching::ALT && (depth & 1));
+}
+
+// MinBranch over the unscheduled positions [lo, hi): lbF(k) / lbB(k) give the
+// two directions' bounds of the job at position k.
+template <class F, class B>
+inline bool choose_minbranch(int lo, int hi, int best, F&& lbF, B&& lbB) {
+  int cntF = 0, cntB = 0;
+  long long sumF = 0, sumB = 0;
+  for (int k = lo; k < hi; k++) {
+    const int f = lbF(k), b = lbB(k);
+    cntF += f < best;
+    cntB += b < best;
+    sumF += f;
+    sumB += b;
+  }
+  return minbranch_backward(cntF, cntB, sumF, sumB);
+}
+
+// Backward / alternating / dynamic branching (all three bounds; minbranch
+// for lb1_d only). Pruning and leaf rules are those of the forward decompose.
+void decompose_bi(const PfspInstance& I, LbKind lb, const PFSPNode& parent, uint64_t& tree,
+                  uint64_t& sol, int& best, Pool<PFSPNode>& pool) {
+  const int jobs = I.jobs;
+  const int limit1 = parent.limit1, limit2 = jobs - parent.nback;
+  const bool leaf = parent.depth + 1 == jobs;
+  int lb_begin[MAX_JOBS], lb_end[MAX_JOBS];
+  bool back;
+  if (I.br == Branching::MINBRANCH) {
+    if (lb != LbKind::LB1_D) check_branching_supported(lb, I.br, false);
+    lb1_children_bounds_bi(I.lb1, parent.prmu, limit1, limit2, lb_begin, lb_end);
+    back = choose_minbranch(
+        limit1 + 1, limit2, best, [&](int k) { return lb_begin[parent.prmu[k]]; },
+        [&](int k) { return lb_end[parent.prmu[k]]; });
+  } else {
+    back = static_backward(I.br, parent.depth);
+    if (lb == LbKind::LB1_D)
+      lb1_children_bounds_bi(I.lb1, parent.prmu, limit1, limit2, back ? nullptr : lb_begin,
+                             back ? lb_end : nullptr);
+  }
+  for (int i = limit1 + 1; i < limit2; i++) {
+    const PFSPNode child = back ? make_child_back(parent, jobs, i) : make_child_front(parent, i);
+    int b;
+    if (lb == LbKind::LB1_D)
+      b = (back ? lb_end : lb_begin)[parent.prmu[i]];
+    else if (lb == LbKind::LB1)
+      b = lb1_bound(I.lb1, child.prmu, child.limit1, jobs - child.nback);
+    else
+      b = lb2_bound(I.lb1, I.lb2, child.prmu, child.limit1, jobs - child.nback, best);
+    if (leaf) {
+      sol += 1;
+      if (b < best) best = b;
+    } else if (b < best) {
+      pool.pushBack(child);
+      tree += 1;
+    }
+  }
+}
+
 }  // namespace
 
 void pfsp_decompose(const PfspInstance& I, LbKind lb, const PFSPNode& parent, uint64_t& tree,
                     uint64_t& sol, int& best, Pool<PFSPNode>& pool) {
+  if (I.br != Branching::FWD) {
+    decompose_bi(I, lb, parent, tree, sol, best, pool);
+    return;
+  }
   switch (lb) {
     case LbKind::LB1:
       decompose_lb1(I, parent, tree, sol, best, pool);
@@ -255,10 +388,12 @@ void pfsp_decompose(const PfspInstance& I, LbKind lb, const PFSPNode& parent, ui
   }
 }
 
-Result pfsp_seq(int inst, const std::string& lb_str, int ub) {
+Result pfsp_seq(int inst, const std::string& lb_str, int ub, const std::string& br_str) {
   const LbKind lb = lb_from_string(lb_str);
+  const Branching br = branching_from_string(br_str);
+  check_branching_supported(lb, br, false);
   Result r;
-  PfspInstance I = make_pfsp_instance(inst, ub);
+  PfspInstance I = make_pfsp_instance(inst, ub, br);
   int best = I.init_ub;
   Pool<PFSPNode> pool;
   pool.pushBack(pfsp_root());
@@ -293,6 +428,35 @@ void pfsp_generate_children(const PfspInstance& I, const PFSPNode* parents, size
         if (lb < best) best = lb;
       } else if (lb < best) {
         pool.pushBack(make_child(parent, j));
+        tree += 1;
+      }
+    }
+  }
+}
+
+void pfsp_generate_children_bi(const PfspInstance& I, const PFSPNode* parents, size_t n,
+                               const int32_t* lb_begin, const int32_t* lb_end,
+                               uint64_t& tree, uint64_t& sol, int& best,
+                               Pool<PFSPNode>& pool) {
+  const int jobs = I.jobs;
+  for (size_t i = 0; i < n; i++) {
+    const PFSPNode& parent = parents[i];
+    const int lo = parent.limit1 + 1, hi = jobs - parent.nback;
+    const int32_t* f = lb_begin + i * jobs;
+    const int32_t* b = lb_end + i * jobs;
+    const bool back =
+        I.br == Branching::MINBRANCH
+            ? choose_minbranch(
+                  lo, hi, best, [&](int k) { return f[k]; }, [&](int k) { return b[k]; })
+            : static_backward(I.br, parent.depth);
+    const bool leaf = parent.depth + 1 == jobs;
+    for (int j = lo; j < hi; j++) {
+      const int lb = back ? b[j] : f[j];
+      if (leaf) {
+        sol += 1;
+        if (lb < best) best = lb;
+      } else if (lb < best) {
+        pool.pushBack(back ? make_child_back(parent, jobs, j) : make_child_front(parent, j));
         tree += 1;
       }
     }

@@ -67,17 +67,49 @@ void nq_bfs_level(int N, int g, size_t target, Pool<NQNode>& pool, uint64_t& tre
 
 // ---------------- PFSP ----------------
 
+// Branching rule (beyond the reference, which branches forward only,
+// pfsp_chpl.chpl:29-32). A node fixes jobs at the front (limit1) and at the
+// back (nback) of the permutation; the rule picks, per parent, on which side
+// its children fix their job:
+//   FWD        always the front (the reference's tree; the default)
+//   BWD        always the back
+//   ALT        front when the parent's depth is even, back when odd
+//   MINBRANCH  (lb1_d only) the side with fewer children surviving the
+//              incumbent; on a tie the side with the larger bound sum
+enum class Branching { FWD = 0, BWD = 1, ALT = 2, MINBRANCH = 3 };
+Branching branching_from_string(const std::string& s);
+const char* branching_name(Branching br);
+// Throws std::invalid_argument naming the combination when `lb` has no
+// implementation of `br` (minbranch needs both directions' bounds of every
+// child, which only lb1_d produces in one pass). gpu_tier adds the GPU tier's
+// restriction: its bi-directional kernels exist for lb1_d only.
+void check_branching_supported(LbKind lb, Branching br, bool gpu_tier);
+
+// A pool handed in from outside (the *_from_pool entry points): under fwd the
+// decompose rules and the forward kernels take limit2 == jobs for granted, so
+// a node with jobs fixed at the back (e.g. a minbranch frontier passed on
+// without its rule) throws std::invalid_argument instead of silently
+// searching another tree.
+void check_pfsp_pool(const PFSPNode* nodes, size_t n, Branching br);
+
+// MinBranch decision from the two directions' survivor counts and bound sums:
+// true = branch backward.
+inline bool minbranch_backward(int cntF, int cntB, long long sumF, long long sumB) {
+  return cntB < cntF || (cntB == cntF && sumB > sumF);
+}
+
 struct PfspInstance {
   int inst = 0, jobs = 0, machines = 0, init_ub = 0;
+  Branching br = Branching::FWD;
   Lb1Data lb1;
   Lb2Data lb2;
 };
-PfspInstance make_pfsp_instance(int inst, int ub);
+PfspInstance make_pfsp_instance(int inst, int ub, Branching br = Branching::FWD);
 
 void pfsp_decompose(const PfspInstance& I, LbKind lb, const PFSPNode& parent, uint64_t& tree,
                     uint64_t& sol, int& best, Pool<PFSPNode>& pool);
 
-Result pfsp_seq(int inst, const std::string& lb, int ub);
+Result pfsp_seq(int inst, const std::string& lb, int ub, const std::string& br = "fwd");
 
 void pfsp_bfs_until(const PfspInstance& I, LbKind lb, size_t target, Pool<PFSPNode>& pool,
                     uint64_t& tree, uint64_t& sol, int& best);
@@ -88,6 +120,15 @@ void pfsp_bfs_until(const PfspInstance& I, LbKind lb, size_t target, Pool<PFSPNo
 void pfsp_generate_children(const PfspInstance& I, const PFSPNode* parents, size_t n,
                             const int32_t* bounds, uint64_t& tree, uint64_t& sol, int& best,
                             Pool<PFSPNode>& pool);
+
+// Both-directions variant (hostpool, lb1_d, non-fwd rules): lb_begin / lb_end
+// hold, per parent and POSITION j, the bound of the child that fixes prmu[j]
+// at the front / at the back. The direction is chosen per parent on the host
+// by I.br, with the same rule as the sequential decompose.
+void pfsp_generate_children_bi(const PfspInstance& I, const PFSPNode* parents, size_t n,
+                               const int32_t* lb_begin, const int32_t* lb_end,
+                               uint64_t& tree, uint64_t& sol, int& best,
+                               Pool<PFSPNode>& pool);
 
 // N-Queens variant from GPU safety labels (nqueens_gpu_chpl.chpl:126-149).
 void nq_generate_children(const NQNode* parents, size_t n, int N, const uint8_t* labels,
