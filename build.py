@@ -23,6 +23,7 @@ SOURCES = [
     "kernels.hip",
     "engine_gpu.cpp",
     "engine_multi.cpp",
+    "engine_testing.cpp",
     "bindings.cpp",
 ]
 

@@ -33,19 +33,12 @@
 #include <vector>
 
 #include "engine_gpu.hpp"
+#include "engine_internal.hpp"
 #include "gpu_api.hpp"
 #include "search_host.hpp"
 #include "taillard.hpp"
 
 namespace gats {
-
-#define HIP_CHECK(expr)                                                              \
-  do {                                                                               \
-    hipError_t _e = (expr);                                                          \
-    if (_e != hipSuccess)                                                            \
-      throw std::runtime_error(std::string("HIP error: ") + hipGetErrorString(_e) +  \
-                               " at " #expr);                                        \
-  } while (0)
 
 int gpu_device_count() {
   int n = 0;
@@ -80,6 +73,8 @@ BufferCache& buffer_cache() {
   static BufferCache c;
   return c;
 }
+
+}  // namespace
 
 void* cached_dev_alloc(size_t bytes) {
   int dev = 0;
@@ -127,6 +122,8 @@ void cached_pinned_free(void* p, size_t bytes) {
   buffer_cache().pinned[{0, bytes}].push_back(p);
 }
 
+namespace {
+
 template <typename T>
 T* dev_alloc(size_t n) {
   return static_cast<T*>(cached_dev_alloc(n * sizeof(T)));
@@ -139,42 +136,33 @@ T* dev_upload(const T* src, size_t n) {
   return d;
 }
 
+}  // namespace
 
-// Owns the int16/uint8-compressed PFSP bound tables on device.
-struct PfspTablesGuard {
-  PfspDevTables tb{};
-  std::vector<void*> allocs;
+PfspTablesGuard::PfspTablesGuard(const PfspInstance& I) {
+  const int n = I.jobs, m = I.machines;
+  std::vector<int16_t> p16(static_cast<size_t>(m) * n);
+  for (size_t i = 0; i < p16.size(); i++) p16[i] = static_cast<int16_t>(I.lb1.p_times[i]);
+  std::vector<int32_t> mt(I.lb1.min_tails.begin(), I.lb1.min_tails.end());
+  const PfspPackedTables pk = build_packed_johnson(I);
+  tb.p_times = keep(dev_upload(p16.data(), p16.size()), p16.size() * sizeof(p16[0]));
+  tb.min_tails = keep(dev_upload(mt.data(), mt.size()), mt.size() * sizeof(mt[0]));
+  tb.johnson_packed =
+      keep(dev_upload(pk.jp.data(), pk.jp.size()), pk.jp.size() * sizeof(uint32_t));
+  tb.pairs1 = keep(dev_upload(pk.p1.data(), pk.p1.size()), pk.p1.size());
+  tb.pairs2 = keep(dev_upload(pk.p2.data(), pk.p2.size()), pk.p2.size());
+  tb.johnson_packed_w =
+      keep(dev_upload(pk.jp_w.data(), pk.jp_w.size()), pk.jp_w.size() * sizeof(uint32_t));
+  tb.pairs1_w = keep(dev_upload(pk.p1_w.data(), pk.p1_w.size()), pk.p1_w.size());
+  tb.pairs2_w = keep(dev_upload(pk.p2_w.data(), pk.p2_w.size()), pk.p2_w.size());
+  std::vector<int32_t> mh(I.lb1.min_heads.begin(), I.lb1.min_heads.end());
+  tb.min_heads = keep(dev_upload(mh.data(), mh.size()), mh.size() * sizeof(mh[0]));
+}
 
-  PfspTablesGuard(const PfspInstance& I) {
-    const int n = I.jobs, m = I.machines;
-    std::vector<int16_t> p16(static_cast<size_t>(m) * n);
-    for (size_t i = 0; i < p16.size(); i++) p16[i] = static_cast<int16_t>(I.lb1.p_times[i]);
-    std::vector<int32_t> mt(I.lb1.min_tails.begin(), I.lb1.min_tails.end());
-    const PfspPackedTables pk = build_packed_johnson(I);
-    tb.p_times = keep(dev_upload(p16.data(), p16.size()), p16.size() * sizeof(p16[0]));
-    tb.min_tails = keep(dev_upload(mt.data(), mt.size()), mt.size() * sizeof(mt[0]));
-    tb.johnson_packed =
-        keep(dev_upload(pk.jp.data(), pk.jp.size()), pk.jp.size() * sizeof(uint32_t));
-    tb.pairs1 = keep(dev_upload(pk.p1.data(), pk.p1.size()), pk.p1.size());
-    tb.pairs2 = keep(dev_upload(pk.p2.data(), pk.p2.size()), pk.p2.size());
-    tb.johnson_packed_w =
-        keep(dev_upload(pk.jp_w.data(), pk.jp_w.size()), pk.jp_w.size() * sizeof(uint32_t));
-    tb.pairs1_w = keep(dev_upload(pk.p1_w.data(), pk.p1_w.size()), pk.p1_w.size());
-    tb.pairs2_w = keep(dev_upload(pk.p2_w.data(), pk.p2_w.size()), pk.p2_w.size());
-    std::vector<int32_t> mh(I.lb1.min_heads.begin(), I.lb1.min_heads.end());
-    tb.min_heads = keep(dev_upload(mh.data(), mh.size()), mh.size() * sizeof(mh[0]));
-  }
-  std::vector<size_t> alloc_bytes;
-  template <typename T>
-  T* keep(T* p, size_t bytes) {
-    allocs.push_back(p);
-    alloc_bytes.push_back(bytes);
-    return p;
-  }
-  ~PfspTablesGuard() {
-    for (size_t i = 0; i < allocs.size(); i++) cached_dev_free(allocs[i], alloc_bytes[i]);
-  }
-};
+PfspTablesGuard::~PfspTablesGuard() {
+  for (size_t i = 0; i < allocs.size(); i++) cached_dev_free(allocs[i], alloc_bytes[i]);
+}
+
+namespace {
 
 // Parked worker threads reused across searches (the persistent-engine thread
 // component): spawning slice threads per search costs ~50-100 us each and the
@@ -258,56 +246,36 @@ StreamCache& stream_cache() {
   return c;
 }
 
-struct StreamGuard {
-  hipStream_t s{};
-  int dev = 0;
-  static bool caching() {
-    static const char* e = std::getenv("GATS_STREAM_CACHE");
-    static const bool on = (e == nullptr) || std::string(e) != "0";
-    return on;
-  }
-  StreamGuard() {
-    (void)hipGetDevice(&dev);
-    if (caching()) {
-      std::lock_guard<std::mutex> l(stream_cache().mu);
-      auto& v = stream_cache().free_[dev];
-      if (!v.empty()) {
-        s = v.back();
-        v.pop_back();
-        return;
-      }
-    }
-    HIP_CHECK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-  }
-  ~StreamGuard() {
-    if (caching()) {
-      std::lock_guard<std::mutex> l(stream_cache().mu);
-      stream_cache().free_[dev].push_back(s);
-    } else {
-      (void)hipStreamDestroy(s);
+}  // namespace
+
+bool StreamGuard::caching() {
+  static const char* e = std::getenv("GATS_STREAM_CACHE");
+  static const bool on = (e == nullptr) || std::string(e) != "0";
+  return on;
+}
+
+StreamGuard::StreamGuard() {
+  (void)hipGetDevice(&dev);
+  if (caching()) {
+    std::lock_guard<std::mutex> l(stream_cache().mu);
+    auto& v = stream_cache().free_[dev];
+    if (!v.empty()) {
+      s = v.back();
+      v.pop_back();
+      return;
     }
   }
-};
+  HIP_CHECK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+}
 
-template <typename T>
-struct DevGuard {
-  T* p = nullptr;
-  size_t bytes = 0;
-  explicit DevGuard(size_t n) : bytes(n * sizeof(T)) {
-    p = static_cast<T*>(cached_dev_alloc(bytes));
+StreamGuard::~StreamGuard() {
+  if (caching()) {
+    std::lock_guard<std::mutex> l(stream_cache().mu);
+    stream_cache().free_[dev].push_back(s);
+  } else {
+    (void)hipStreamDestroy(s);
   }
-  ~DevGuard() { cached_dev_free(p, bytes); }
-};
-
-template <typename T>
-struct PinnedGuard {
-  T* p = nullptr;
-  size_t bytes = 0;
-  explicit PinnedGuard(size_t n) : bytes(n * sizeof(T)) {
-    p = static_cast<T*>(cached_pinned_alloc(bytes));
-  }
-  ~PinnedGuard() { cached_pinned_free(p, bytes); }
-};
+}
 
 // PFSP device bound tables are immutable per instance: build + upload once
 // per (device, instance) and share across searches/slices (rebuilding cost a
@@ -322,8 +290,6 @@ const PfspDevTables& pfsp_tables_cached(const PfspInstance& I, int device) {
     it = cache.emplace(key, new PfspTablesGuard(I)).first;  // lives for the process
   return it->second->tb;
 }
-
-}  // namespace
 
 PfspPackedTables build_packed_johnson(const PfspInstance& I) {
   const int n = I.jobs;
@@ -386,81 +352,6 @@ PfspPackedTables build_packed_johnson(const PfspInstance& I) {
   }
   return pk;
 }
-
-namespace {
-
-int lbk_of(LbKind lb) {
-  switch (lb) {
-    case LbKind::LB1_D:
-      return 0;
-    case LbKind::LB1:
-      return 1;
-    default:
-      return 2;
-  }
-}
-
-// Device buffers of one devpool (one slice thread, frontier builder or
-// single-step call). gsum may be a 1-entry dummy when presum is never used.
-template <class NodeT>
-struct DevIterBufs {
-  NodeT* pool;
-  NodeT* childbuf;
-  uint32_t* bc;
-  unsigned long long* bs;
-  unsigned long long* be;  // N-Queens finisher counts; unused for PFSP
-  uint32_t* gsum;
-  int stride;
-  unsigned long long capacity;
-};
-
-// ONE devpool iteration: expand -> (group presum) -> gather2. Every engine
-// loop and the single-step test entry points enqueue exactly this sequence;
-// iteration i reads `cur` and gather2's last block writes `next`. Mi is the
-// chunk window the grids are sized for (callers clamp it to a bound on the
-// live pool size, which leaves the pop rule min(size, M) unchanged).
-void enqueue_nq_iter(const DevIterBufs<NQNode>& b, DevCtl* cur, DevCtl* next, int N, int g,
-                     int finish, unsigned long long m, unsigned long long Mi, bool presum,
-                     hipStream_t s) {
-  const int Gi = devpool_grid(Mi, N, 1);
-  launch_nq_x(cur, b.pool, b.childbuf, b.bc, b.bs, b.be, N, g, finish, m, Mi, s);
-  if (presum) launch_presum(b.bc, b.gsum, Gi, s);
-  launch_gather2_nq(cur, next, b.bc, b.bs, b.be, presum ? b.gsum : nullptr, b.childbuf,
-                    b.pool, b.stride, Gi, m, Mi, b.capacity, s);
-}
-
-void enqueue_pfsp_iter(const DevIterBufs<PFSPNode>& b, DevCtl* cur, DevCtl* next, int jobs,
-                       int machines, int lbg, const PfspDevTables& tb, unsigned long long m,
-                       unsigned long long Mi, bool presum, hipStream_t s, int br = 0) {
-  const int Gi = devpool_grid(Mi, jobs, lbg);
-  launch_pfsp_x(cur, b.pool, b.childbuf, b.bc, b.bs, jobs, machines, lbg, tb, m, Mi, s, br);
-  if (presum) launch_presum(b.bc, b.gsum, Gi, s);
-  launch_gather2_pfsp(cur, next, b.bc, b.bs, presum ? b.gsum : nullptr, b.childbuf, b.pool,
-                      b.stride, Gi, m, Mi, b.capacity, s);
-}
-
-// Per-iteration launch policy of the devpool engine threads (and of the chain
-// test entry points, so that they launch what the engines launch): the grid
-// window Mi covers only the chunk that can exist (bound >= pool size, so
-// min(size, Mi) == min(size, Mc): the pop rule is unchanged), and the group
-// presum runs only where the buffers were sized for it (presum_alloc) and the
-// prefix walk is long enough to pay for the extra launch.
-struct DevIterPolicy {
-  unsigned long long Mi;
-  bool ps;
-};
-
-bool devpool_presum_alloc(int G, int lbg) { return lbg == 2 || G > 1024; }
-
-DevIterPolicy devpool_iter_policy(unsigned long long Mc, unsigned long long bound, int per,
-                                  int lbg, bool presum_alloc) {
-  const unsigned long long Mi = std::min(Mc, std::max<unsigned long long>(bound, 1));
-  const bool ps = presum_alloc && (lbg == 2 || devpool_grid(Mi, per, lbg) > 256);
-  return {Mi, ps};
-}
-
-}  // namespace
-
 
 // Shared devpool driver: capture BATCH iterations into a hipGraph once, then
 // replay + poll the 48 B control block until the pool drops below m
@@ -646,7 +537,6 @@ static DevCtl run_devpool_loop(hipStream_t s, DevCtl* ctl_d, const DevLoopCfg& c
   return *ctl_h.p;
 }
 
-
 // ---------------------------------------------------------------------------
 // Multi-slice devpool: S independent device pools driven on S HIP streams by
 // S host threads — ONE devpool loop is a serial expand->gather dependency
@@ -720,11 +610,7 @@ struct SliceShare {
   int offer_best = 0;
 };
 
-// Queue-driven worker thread: allocates its device buffers once, then keeps
-// claiming frontier slices from the shared index until none remain. Slices
-// are oversubscribed (~4 per thread) so a thread whose slice finishes early
-// just pulls the next one — tail balancing without inter-thread stealing.
-// Generic steal-share helpers for a slice thread (node type erased to bytes).
+// Steal-share helpers for a slice thread.
 // Donor side: runs at readback boundaries (stream idle); carves the BACK half
 // of the live pool when someone is waiting and the pool holds >= 2m nodes,
 // then blocks (bounded waits) until the thief's D2D copy acks.
@@ -831,226 +717,93 @@ struct RunnerScope {
   }
 };
 
-static SliceOut devpool_thread_nq(const std::vector<std::vector<NQNode>>& slices,
-                                  std::atomic<int>& next_slice, int N, int g, int m, int M,
-                                  int device, int finish, unsigned long long capacity,
-                                  bool allow_graph, SliceShare* share,
-                                  std::vector<NQNode>& leftover) {
-  set_device_cached(device);
-  StreamGuard stream;
-  SliceOut out;
-  Result& r = out.diag;
-  const unsigned long long Mc = devpool_chunk_cap(M, N, capacity, 1);
-  DevGuard<NQNode> pool_d(capacity);
-  DevGuard<DevCtl> ctl_d(2);  // parity-alternating control blocks
-  const int G = devpool_grid(Mc, N, 1);
-  const int stride = devpool_stride(1);
-  DevGuard<NQNode> childbuf_d(static_cast<size_t>(G) * stride);
-  DevGuard<uint32_t> bc_d(G);
-  DevGuard<unsigned long long> bs_d(G), be_d(G);
-  // group sums keep gather's prefix walk O(G/256): at the wide chunk G is
-  // ~8700 blocks and the linear walk dominated gather (193 us avg at N=17)
-  const bool presum = devpool_presum_alloc(G, 1);
-  DevGuard<uint32_t> gsum_d(presum ? (G + 255) / 256 : 1);
-  std::vector<NQNode> spilled;  // capacity-pressure spill, re-run after the slice
-  const DevIterBufs<NQNode> bufs{pool_d.p, childbuf_d.p, bc_d.p,  bs_d.p,
-                                 be_d.p,   gsum_d.p,     stride, capacity};
+// What a slice thread's readback and spill hooks see: the host copy of the
+// live control block, its device address, the thread's pool and stream (idle
+// at that point) and the thread's counters.
+template <class NodeT>
+struct SliceReadback {
+  DevCtl* hc;
+  DevCtl* live;
+  const NodeT* pool_d;
+  hipStream_t s;
+  Result& r;
+};
+template <class NodeT>
+using SliceReadbackFn = std::function<void(const SliceReadback<NodeT>&)>;
 
-  auto iter = [&](int parity, unsigned long long bound) {
-    const DevIterPolicy it = devpool_iter_policy(Mc, bound, N, 1, presum);
-    enqueue_nq_iter(bufs, ctl_d.p + parity, ctl_d.p + (1 - parity), N, g, finish, m, it.Mi,
-                    it.ps, stream.s);
-  };
-  ReadbackHook hook = [&](DevCtl* hc, DevCtl* live) {
-    donate_if_wanted(share, hc, live, pool_d.p, m, stream.s);
-  };
-  ReadbackHook spill = [&](DevCtl* hc, DevCtl* live) {
-    const unsigned long long half = hc->size / 2;
-    if (half == 0) return;
-    const unsigned long long newsize = hc->size - half;
-    const size_t base = spilled.size();
-    spilled.resize(base + half);
-    HIP_CHECK(hipMemcpyAsync(spilled.data() + base, pool_d.p + newsize,
-                             half * sizeof(NQNode), hipMemcpyDeviceToHost, stream.s));
-    HIP_CHECK(hipMemcpyAsync(&live->size, &newsize, sizeof(newsize),
-                             hipMemcpyHostToDevice, stream.s));
-    HIP_CHECK(hipStreamSynchronize(stream.s));
-    hc->size = newsize;
-    r.d2h++;
-    r.d2h_bytes += half * sizeof(NQNode);
-  };
-
-  DevLoopCfg cfg;
-  cfg.m = m;
-  cfg.capacity = capacity;
-  cfg.growth = Mc * N;  // worst-case children/iter
-  cfg.per = N;
-  cfg.allow_graph = allow_graph;
-
-  auto run_pool = [&](unsigned long long init_size) {
-    DevCtl ctl{};
-    ctl.size = init_size;
-    HIP_CHECK(hipMemcpyAsync(ctl_d.p, &ctl, sizeof(DevCtl), hipMemcpyHostToDevice, stream.s));
-    HIP_CHECK(
-        hipMemcpyAsync(ctl_d.p + 1, &ctl, sizeof(DevCtl), hipMemcpyHostToDevice, stream.s));
-    HIP_CHECK(hipStreamSynchronize(stream.s));  // ctl is a stack temporary
-    r.h2d += 2;
-    r.h2d_bytes += 2 * sizeof(DevCtl);
-    cfg.init_size = init_size;
-    RunnerScope runner(share);
-    const DevCtl fin = run_devpool_loop(stream.s, ctl_d.p, cfg, iter, r, nullptr, hook,
-                                        spill);
-    out.fin.tree += fin.tree;
-    out.fin.sol += fin.sol;
-    r.gpu_iters += fin.iters;
-    if (fin.size > 0) {
-      const size_t base = leftover.size();
-      leftover.resize(base + fin.size);
-      HIP_CHECK(hipMemcpyAsync(leftover.data() + base, pool_d.p, fin.size * sizeof(NQNode),
-                               hipMemcpyDeviceToHost, stream.s));
-      HIP_CHECK(hipStreamSynchronize(stream.s));
-      r.d2h++;
-      r.d2h_bytes += fin.size * sizeof(NQNode);
-    }
-  };
-  // re-run anything the capacity spill pushed out (it may spill again; the
-  // stack shrinks by at least half the capacity per round)
-  auto drain_spilled = [&]() {
-    while (!spilled.empty()) {
-      const size_t take = std::min<size_t>(spilled.size(), capacity / 2);
-      std::vector<NQNode> chunk(spilled.end() - take, spilled.end());
-      spilled.resize(spilled.size() - take);
-      HIP_CHECK(hipMemcpyAsync(pool_d.p, chunk.data(), take * sizeof(NQNode),
-                               hipMemcpyHostToDevice, stream.s));
-      r.h2d++;
-      r.h2d_bytes += take * sizeof(NQNode);
-      run_pool(take);
-    }
-  };
-
-  int si;
-  while ((si = next_slice.fetch_add(1)) < static_cast<int>(slices.size())) {
-    const std::vector<NQNode>& nodes = slices[si];
-    if (nodes.empty()) continue;
-    if (nodes.size() > capacity) throw std::runtime_error("devpool capacity too small");
-    // per-stream async copies: synchronous hipMemcpy runs on the NULL stream
-    // and would serialize every slice thread at each slice boundary
-    HIP_CHECK(hipMemcpyAsync(pool_d.p, nodes.data(), nodes.size() * sizeof(NQNode),
-                             hipMemcpyHostToDevice, stream.s));
-    r.h2d++;
-    r.h2d_bytes += nodes.size() * sizeof(NQNode);
-    run_pool(nodes.size());
-    drain_spilled();
+// MOVE the back half of the live pool to host memory: copy it to
+// dest(half), shrink the size in both copies of the control block, wait, and
+// count the transfer. `dest_mu`, when given, is held while dest() makes room
+// and the copy is enqueued.
+template <class NodeT, class Dest>
+static void carve_back_half(const SliceReadback<NodeT>& rb, std::mutex* dest_mu, Dest&& dest) {
+  const unsigned long long half = rb.hc->size / 2;
+  const unsigned long long newsize = rb.hc->size - half;
+  {
+    std::unique_lock<std::mutex> l;
+    if (dest_mu) l = std::unique_lock<std::mutex>(*dest_mu);
+    HIP_CHECK(hipMemcpyAsync(dest(half), rb.pool_d + newsize, half * sizeof(NodeT),
+                             hipMemcpyDeviceToHost, rb.s));
   }
-
-  // queue drained: take donated halves of still-running slices until no
-  // runner remains (ROADMAP item 2, landed)
-  while (share) {
-    StolenWork w;
-    if (!wait_for_work(*share, w)) break;
-    HIP_CHECK(hipMemcpyAsync(pool_d.p, w.src, w.n * sizeof(NQNode), hipMemcpyDeviceToDevice,
-                             stream.s));
-    HIP_CHECK(hipStreamSynchronize(stream.s));
-    ack_taken(*share);
-    run_pool(w.n);
-    drain_spilled();
-  }
-  return out;
+  HIP_CHECK(hipMemcpyAsync(&rb.live->size, &newsize, sizeof(newsize), hipMemcpyHostToDevice,
+                           rb.s));
+  HIP_CHECK(hipStreamSynchronize(rb.s));
+  rb.hc->size = newsize;
+  rb.r.d2h++;
+  rb.r.d2h_bytes += half * sizeof(NodeT);
 }
 
-static SliceOut devpool_thread_pfsp(const std::vector<std::vector<PFSPNode>>& slices,
-                                    std::atomic<int>& next_slice, const PfspInstance& I,
-                                    int lbk, int best0,
-                                    int m, int M, int device, unsigned long long capacity,
-                                    std::atomic<int>* shared_best, bool allow_graph,
-                                    SliceShare* share, std::vector<PFSPNode>& leftover,
-                                    ExtractShare* extract) {
+// Queue-driven slice thread: allocates its device buffers once, then keeps
+// claiming frontier slices from the shared index until none remain. Slices
+// are oversubscribed (~4 per thread) so a thread whose slice finishes early
+// just pulls the next one; once the queue is empty it takes donated
+// half-pools of same-device threads (SliceShare). `shared_best` (optional) is
+// the cross-thread incumbent handed to run_devpool_loop: without it nothing is
+// published or written to the device. `on_readback` (optional) runs after
+// the donation check at every readback boundary.
+template <class Problem>
+static SliceOut devpool_thread(const Problem& problem,
+                               const std::vector<std::vector<typename Problem::Node>>& slices,
+                               std::atomic<int>& next_slice, int best0, int m, int M,
+                               int device, unsigned long long capacity,
+                               std::atomic<int>* shared_best, bool allow_graph,
+                               SliceShare* share,
+                               std::vector<typename Problem::Node>& leftover,
+                               const SliceReadbackFn<typename Problem::Node>& on_readback) {
+  using NodeT = typename Problem::Node;
   set_device_cached(device);
-  const PfspDevTables& tb = pfsp_tables_cached(I, device);
+  const Problem P = problem.on_device(device);
   StreamGuard stream;
   SliceOut out;
   out.fin.best = best0;
   Result& r = out.diag;
-  const int jobs = I.jobs, machines = I.machines;
-  const int lbg = devpool_lbk_geom(lbk, machines);  // 3 = per-lane lb2
-  const unsigned long long Mc = devpool_chunk_cap(M, jobs, capacity, lbg);
-  DevGuard<PFSPNode> pool_d(capacity);
-  DevGuard<DevCtl> ctl_d(2);
-  const int G = devpool_grid(Mc, jobs, lbg);
-  const int stride = devpool_stride(lbg);
-  DevGuard<PFSPNode> childbuf_d(static_cast<size_t>(G) * stride);
-  DevGuard<uint32_t> bc_d(G);
-  DevGuard<unsigned long long> bs_d(G);
-  // group sums keep gather's prefix walk O(G/256) (always needed for lb2's
-  // per-wave counts; needed for thread-per-child paths once the chunk is wide)
-  const bool presum = devpool_presum_alloc(G, lbg);
-  DevGuard<uint32_t> gsum_d(presum ? (G + 255) / 256 : 1);
-
-  std::vector<PFSPNode> spilled;  // capacity-pressure spill, re-run after the slice
-  const DevIterBufs<PFSPNode> bufs{pool_d.p, childbuf_d.p, bc_d.p,  bs_d.p,
-                                   nullptr,  gsum_d.p,     stride, capacity};
+  const unsigned long long Mc = devpool_chunk_cap(M, P.per, capacity, P.lbg);
+  const bool presum = devpool_presum_alloc(devpool_grid(Mc, P.per, P.lbg), P.lbg);
+  const DevpoolBufs<NodeT> bufs(capacity, Mc, P.per, P.lbg, Problem::needs_be, presum);
+  std::vector<NodeT> spilled;  // capacity-pressure spill, re-run after the slice
 
   auto iter = [&](int parity, unsigned long long bound) {
-    const DevIterPolicy it = devpool_iter_policy(Mc, bound, jobs, lbg, presum);
-    enqueue_pfsp_iter(bufs, ctl_d.p + parity, ctl_d.p + (1 - parity), jobs, machines, lbg, tb,
-                      m, it.Mi, it.ps, stream.s, static_cast<int>(I.br));
+    const DevIterPolicy it = devpool_iter_policy(Mc, bound, P.per, P.lbg, presum);
+    P.enqueue(bufs, bufs.ctl.p + parity, bufs.ctl.p + (1 - parity), m, it.Mi, it.ps, stream.s);
   };
   ReadbackHook hook = [&](DevCtl* hc, DevCtl* live) {
-    donate_if_wanted(share, hc, live, pool_d.p, m, stream.s);
-    if (extract) {
-      extract->live_size.store(hc->size, std::memory_order_relaxed);
-      int want = ExtractShare::WANTED;
-      if (extract->state.load(std::memory_order_relaxed) == want &&
-          hc->size >= 2 * static_cast<unsigned long long>(m) &&
-          extract->state.compare_exchange_strong(want, ExtractShare::CARVING,
-                                                 std::memory_order_acq_rel)) {
-        // engine-pausing inter-rank steal: carve the back half to the host
-        // at this (stream-idle) readback boundary; nodes MOVE, never copy,
-        // so counts stay exact. The CARVING state keeps the request visibly
-        // pending until the nodes are READY to take.
-        const unsigned long long half = hc->size / 2;
-        const unsigned long long newsize = hc->size - half;
-        {
-          std::lock_guard<std::mutex> l(extract->mu);
-          extract->taken.resize(half);
-          HIP_CHECK(hipMemcpyAsync(extract->taken.data(), pool_d.p + newsize,
-                                   half * sizeof(PFSPNode), hipMemcpyDeviceToHost,
-                                   stream.s));
-        }
-        HIP_CHECK(hipMemcpyAsync(&live->size, &newsize, sizeof(newsize),
-                                 hipMemcpyHostToDevice, stream.s));
-        HIP_CHECK(hipStreamSynchronize(stream.s));
-        hc->size = newsize;
-        r.d2h++;
-        r.d2h_bytes += half * sizeof(PFSPNode);
-        if (std::getenv("GATS_CARVE_LOG"))
-          fprintf(stderr, "CARVE pool=%p size %llu -> %llu tree=%llu iters=%llu\n",
-                  (void*)pool_d.p, newsize + half, newsize, hc->tree, hc->iters);
-        extract->state.store(ExtractShare::READY, std::memory_order_release);
-      }
-    }
+    donate_if_wanted(share, hc, live, bufs.pool.p, m, stream.s);
+    if (on_readback) on_readback({hc, live, bufs.pool.p, stream.s, r});
   };
   ReadbackHook spill = [&](DevCtl* hc, DevCtl* live) {
-    const unsigned long long half = hc->size / 2;
-    if (half == 0) return;
-    const unsigned long long newsize = hc->size - half;
-    const size_t base = spilled.size();
-    spilled.resize(base + half);
-    HIP_CHECK(hipMemcpyAsync(spilled.data() + base, pool_d.p + newsize,
-                             half * sizeof(PFSPNode), hipMemcpyDeviceToHost, stream.s));
-    HIP_CHECK(hipMemcpyAsync(&live->size, &newsize, sizeof(newsize),
-                             hipMemcpyHostToDevice, stream.s));
-    HIP_CHECK(hipStreamSynchronize(stream.s));
-    hc->size = newsize;
-    r.d2h++;
-    r.d2h_bytes += half * sizeof(PFSPNode);
+    if (hc->size / 2 == 0) return;
+    carve_back_half<NodeT>({hc, live, bufs.pool.p, stream.s, r}, nullptr,
+                           [&](unsigned long long half) {
+                             spilled.resize(spilled.size() + half);
+                             return spilled.data() + (spilled.size() - half);
+                           });
   };
 
   DevLoopCfg cfg;
   cfg.m = m;
   cfg.capacity = capacity;
-  cfg.growth = Mc * jobs;
-  cfg.per = jobs;
+  cfg.growth = Mc * P.per;  // worst-case children/iter
+  cfg.per = P.per;
   cfg.allow_graph = allow_graph;
 
   auto run_pool = [&](unsigned long long init_size, int init_best) {
@@ -1060,15 +813,12 @@ static SliceOut devpool_thread_pfsp(const std::vector<std::vector<PFSPNode>>& sl
     const int sb_now =
         shared_best ? shared_best->load(std::memory_order_relaxed) : init_best;
     ctl.best = sb_now < init_best ? sb_now : init_best;
-    HIP_CHECK(hipMemcpyAsync(ctl_d.p, &ctl, sizeof(DevCtl), hipMemcpyHostToDevice, stream.s));
-    HIP_CHECK(
-        hipMemcpyAsync(ctl_d.p + 1, &ctl, sizeof(DevCtl), hipMemcpyHostToDevice, stream.s));
-    HIP_CHECK(hipStreamSynchronize(stream.s));
+    upload_ctl_pair(bufs.ctl.p, ctl, stream.s);
     r.h2d += 2;
     r.h2d_bytes += 2 * sizeof(DevCtl);
     cfg.init_size = init_size;
     RunnerScope runner(share);
-    const DevCtl fin = run_devpool_loop(stream.s, ctl_d.p, cfg, iter, r, shared_best,
+    const DevCtl fin = run_devpool_loop(stream.s, bufs.ctl.p, cfg, iter, r, shared_best,
                                         hook, spill);
     out.fin.tree += fin.tree;
     out.fin.sol += fin.sol;
@@ -1077,46 +827,50 @@ static SliceOut devpool_thread_pfsp(const std::vector<std::vector<PFSPNode>>& sl
     if (fin.size > 0) {
       const size_t base = leftover.size();
       leftover.resize(base + fin.size);
-      HIP_CHECK(hipMemcpyAsync(leftover.data() + base, pool_d.p,
-                               fin.size * sizeof(PFSPNode), hipMemcpyDeviceToHost,
-                               stream.s));
+      HIP_CHECK(hipMemcpyAsync(leftover.data() + base, bufs.pool.p,
+                               fin.size * sizeof(NodeT), hipMemcpyDeviceToHost, stream.s));
       HIP_CHECK(hipStreamSynchronize(stream.s));
       r.d2h++;
-      r.d2h_bytes += fin.size * sizeof(PFSPNode);
+      r.d2h_bytes += fin.size * sizeof(NodeT);
     }
   };
+  // re-run anything the capacity spill pushed out (it may spill again; the
+  // stack shrinks by at least half the capacity per round)
   auto drain_spilled = [&]() {
     while (!spilled.empty()) {
       const size_t take = std::min<size_t>(spilled.size(), capacity / 2);
-      std::vector<PFSPNode> chunk(spilled.end() - take, spilled.end());
+      std::vector<NodeT> chunk(spilled.end() - take, spilled.end());
       spilled.resize(spilled.size() - take);
-      HIP_CHECK(hipMemcpyAsync(pool_d.p, chunk.data(), take * sizeof(PFSPNode),
+      HIP_CHECK(hipMemcpyAsync(bufs.pool.p, chunk.data(), take * sizeof(NodeT),
                                hipMemcpyHostToDevice, stream.s));
       r.h2d++;
-      r.h2d_bytes += take * sizeof(PFSPNode);
+      r.h2d_bytes += take * sizeof(NodeT);
       run_pool(take, out.fin.best);
     }
   };
 
   int si;
   while ((si = next_slice.fetch_add(1)) < static_cast<int>(slices.size())) {
-    const std::vector<PFSPNode>& nodes = slices[si];
+    const std::vector<NodeT>& nodes = slices[si];
     if (nodes.empty()) continue;
     if (nodes.size() > capacity) throw std::runtime_error("devpool capacity too small");
-    HIP_CHECK(hipMemcpyAsync(pool_d.p, nodes.data(), nodes.size() * sizeof(PFSPNode),
+    // per-stream async copies: synchronous hipMemcpy runs on the NULL stream
+    // and would serialize every slice thread at each slice boundary
+    HIP_CHECK(hipMemcpyAsync(bufs.pool.p, nodes.data(), nodes.size() * sizeof(NodeT),
                              hipMemcpyHostToDevice, stream.s));
     r.h2d++;
-    r.h2d_bytes += nodes.size() * sizeof(PFSPNode);
+    r.h2d_bytes += nodes.size() * sizeof(NodeT);
     run_pool(nodes.size(), best0);
     drain_spilled();
   }
 
-  // queue drained: take donated halves of still-running slices (ROADMAP #2)
+  // queue drained: take donated halves of still-running slices until no
+  // runner remains (ROADMAP item 2, landed)
   while (share) {
     StolenWork w;
     if (!wait_for_work(*share, w)) break;
-    HIP_CHECK(hipMemcpyAsync(pool_d.p, w.src, w.n * sizeof(PFSPNode),
-                             hipMemcpyDeviceToDevice, stream.s));
+    HIP_CHECK(hipMemcpyAsync(bufs.pool.p, w.src, w.n * sizeof(NodeT), hipMemcpyDeviceToDevice,
+                             stream.s));
     HIP_CHECK(hipStreamSynchronize(stream.s));
     ack_taken(*share);
     run_pool(w.n, w.best);
@@ -1144,17 +898,19 @@ static void merge_slice_diag(Result& r, const Result& d) {
 // a same-device D2D copy.
 // ---------------------------------------------------------------------------
 
-DevpoolMultiOut nq_devpool_multi(Pool<NQNode>& pool, int N, int g, int m, int M,
-                                 const std::vector<int>& devices,
-                                 unsigned long long capacity, Result& r) {
-  if (static_cast<unsigned long long>(M) * N > (1ull << 31))
-    throw std::invalid_argument("devpool requires M * N <= 2^31");
-  // depth of the in-thread bitmask subtree finisher (levels from the bottom)
-  int finish = 8;
-  if (const char* e = std::getenv("GATS_NQ_FINISH")) finish = atoi(e);
-  if (finish > 8) finish = 8;  // template recursion budget (NQ_FINISH_MAX)
+// S is the caller's devpool_slices() choice; `deep_levels` its threshold for
+// the deep-frontier rule below. `sb` (optional) is the incumbent the slice
+// threads share; `on_readback` goes to every slice thread.
+template <class Problem>
+static DevpoolMultiOut devpool_multi(const Problem& problem,
+                                     Pool<typename Problem::Node>& pool, int S,
+                                     int deep_levels, int best0, int m, int M,
+                                     const std::vector<int>& devices,
+                                     unsigned long long capacity, std::atomic<int>* sb,
+                                     Result& r,
+                                     const SliceReadbackFn<typename Problem::Node>& on_readback) {
+  using NodeT = typename Problem::Node;
   const int D = static_cast<int>(devices.size());
-  int S = devpool_slices();
   // a frontier of DEEP nodes explodes immediately (a 2048-node N=17 dist
   // sub-slice carries billion-node subtrees), so it deserves full slicing
   // no matter how small the pool is; only genuinely small searches (the
@@ -1162,13 +918,13 @@ DevpoolMultiOut nq_devpool_multi(Pool<NQNode>& pool, int N, int g, int m, int M,
   int maxd = 0;
   for (size_t i = 0; i < pool.size(); i++)
     maxd = std::max(maxd, static_cast<int>(pool.data()[i].depth));
-  if (N - maxd < 10)
+  if (problem.per - maxd < deep_levels)
     while (S > 1 && pool.size() < static_cast<size_t>(D) * S * 2048) S--;
   const int T = D * S;
   const int NS = (T == 1) ? 1 : T * 4;  // oversubscribe: ~4 queued slices/thread
-  std::vector<std::vector<NQNode>> slices(NS);
+  std::vector<std::vector<NodeT>> slices(NS);
   {
-    const NQNode* src = pool.data();
+    const NodeT* src = pool.data();
     const size_t total = pool.size();
     for (int t = 0; t < NS; t++) slices[t].reserve(total / NS + 1);
     for (size_t i = 0; i < total; i++) slices[i % NS].push_back(src[i]);
@@ -1177,77 +933,14 @@ DevpoolMultiOut nq_devpool_multi(Pool<NQNode>& pool, int N, int g, int m, int M,
   std::atomic<int> next_slice{0};
   std::vector<SliceShare> shares(D);
   std::vector<SliceOut> outs(T);
-  std::vector<std::vector<NQNode>> lefts(T);
+  std::vector<std::vector<NodeT>> lefts(T);
   std::vector<std::exception_ptr> errs(T);
   const bool allow_graph = (T == 1);
   run_on_pool(T, [&](int t) {
     try {
       SliceShare* sh = (S > 1) ? &shares[t / S] : nullptr;
-      outs[t] = devpool_thread_nq(slices, next_slice, N, g, m, M, devices[t / S],
-                                  finish, capacity, allow_graph, sh, lefts[t]);
-    } catch (...) {
-      errs[t] = std::current_exception();
-    }
-  });
-  for (auto& e : errs)
-    if (e) std::rethrow_exception(e);
-  DevpoolMultiOut o;
-  o.per_dev.assign(D, 0);
-  for (int t = 0; t < T; t++) {
-    o.tree += outs[t].fin.tree;
-    o.sol += outs[t].fin.sol;
-    o.per_dev[t / S] += outs[t].fin.tree;
-    merge_slice_diag(r, outs[t].diag);
-    if (!lefts[t].empty()) pool.pushBackBulk(lefts[t].data(), lefts[t].size());
-  }
-  return o;
-}
-
-DevpoolMultiOut pfsp_devpool_multi(const PfspInstance& I, Pool<PFSPNode>& pool, int lbk,
-                                   int best0, int m, int M,
-                                   const std::vector<int>& devices,
-                                   unsigned long long capacity,
-                                   std::atomic<int>* shared_best, Result& r,
-                                   ExtractShare* extract) {
-  const int jobs = I.jobs;
-  if (static_cast<unsigned long long>(M) * jobs > (1ull << 31))
-    throw std::invalid_argument("devpool requires M * jobs <= 2^31");
-  if (I.br != Branching::FWD && lbk != 0)
-    throw std::invalid_argument(std::string("branching rule '") + branching_name(I.br) +
-                                "' on the gpu tier needs lb1_d");
-  const int D = static_cast<int>(devices.size());
-  int S = devpool_slices(devpool_lbk_geom(lbk, I.machines));
-  int maxd = 0;  // same deep-frontier rule as N-Queens (12+ open jobs)
-  for (size_t i = 0; i < pool.size(); i++)
-    maxd = std::max(maxd, static_cast<int>(pool.data()[i].depth));
-  if (jobs - maxd < 12)
-    while (S > 1 && pool.size() < static_cast<size_t>(D) * S * 2048) S--;
-  const int T = D * S;
-  const int NS = (T == 1) ? 1 : T * 4;
-  std::vector<std::vector<PFSPNode>> slices(NS);
-  {
-    const PFSPNode* src = pool.data();
-    const size_t total = pool.size();
-    for (int t = 0; t < NS; t++) slices[t].reserve(total / NS + 1);
-    for (size_t i = 0; i < total; i++) slices[i % NS].push_back(src[i]);
-    pool.clear();
-  }
-  // workers share the incumbent through this atomic even when no external
-  // one is plugged in (cross-worker pruning; identical counts at ub=1)
-  std::atomic<int> local_best{best0};
-  std::atomic<int>* sb = shared_best ? shared_best : &local_best;
-  std::atomic<int> next_slice{0};
-  std::vector<SliceShare> shares(D);
-  std::vector<SliceOut> outs(T);
-  std::vector<std::vector<PFSPNode>> lefts(T);
-  std::vector<std::exception_ptr> errs(T);
-  const bool allow_graph = (T == 1);
-  run_on_pool(T, [&](int t) {
-    try {
-      SliceShare* sh = (S > 1) ? &shares[t / S] : nullptr;
-      outs[t] = devpool_thread_pfsp(slices, next_slice, I, lbk, best0, m, M,
-                                    devices[t / S], capacity, sb, allow_graph, sh,
-                                    lefts[t], extract);
+      outs[t] = devpool_thread(problem, slices, next_slice, best0, m, M, devices[t / S],
+                               capacity, sb, allow_graph, sh, lefts[t], on_readback);
     } catch (...) {
       errs[t] = std::current_exception();
     }
@@ -1265,11 +958,81 @@ DevpoolMultiOut pfsp_devpool_multi(const PfspInstance& I, Pool<PFSPNode>& pool, 
     merge_slice_diag(r, outs[t].diag);
     if (!lefts[t].empty()) pool.pushBackBulk(lefts[t].data(), lefts[t].size());
   }
-  {
+  if (sb) {
     const int sbv = sb->load(std::memory_order_relaxed);
     if (sbv < o.best) o.best = sbv;
   }
   return o;
+}
+
+// GATS_NQ_FINISH: depth of the in-thread bitmask subtree finisher (levels from
+// the bottom), default and upper limit 8 (template recursion budget,
+// NQ_FINISH_MAX).
+static int nq_finish_depth() {
+  int finish = 8;
+  if (const char* e = std::getenv("GATS_NQ_FINISH")) finish = atoi(e);
+  if (finish > 8) finish = 8;
+  return finish;
+}
+
+DevpoolMultiOut nq_devpool_multi(Pool<NQNode>& pool, int N, int g, int m, int M,
+                                 const std::vector<int>& devices,
+                                 unsigned long long capacity, Result& r) {
+  if (static_cast<unsigned long long>(M) * N > (1ull << 31))
+    throw std::invalid_argument("devpool requires M * N <= 2^31");
+  return devpool_multi(NqDevProblem(N, g, nq_finish_depth()), pool, devpool_slices(),
+                       /*deep_levels=*/10, /*best0=*/0, m, M, devices, capacity, nullptr, r,
+                       {});
+}
+
+static void check_devpool_branching(const PfspInstance& I, int lbk) {
+  if (I.br != Branching::FWD && lbk != 0)
+    throw std::invalid_argument(std::string("branching rule '") + branching_name(I.br) +
+                                "' on the gpu tier needs lb1_d");
+}
+
+DevpoolMultiOut pfsp_devpool_multi(const PfspInstance& I, Pool<PFSPNode>& pool, int lbk,
+                                   int best0, int m, int M,
+                                   const std::vector<int>& devices,
+                                   unsigned long long capacity,
+                                   std::atomic<int>* shared_best, Result& r,
+                                   ExtractShare* extract) {
+  if (static_cast<unsigned long long>(M) * I.jobs > (1ull << 31))
+    throw std::invalid_argument("devpool requires M * jobs <= 2^31");
+  check_devpool_branching(I, lbk);
+  const int lbg = devpool_lbk_geom(lbk, I.machines);  // 3 = per-lane lb2
+  // workers share the incumbent through this atomic even when no external
+  // one is plugged in (cross-worker pruning; identical counts at ub=1)
+  std::atomic<int> local_best{best0};
+  // engine-pausing inter-rank steal (ExtractShare): a pending request is
+  // served at this (stream-idle) readback boundary by carving the back half to
+  // the host; nodes MOVE, never copy, so counts stay exact. The CARVING
+  // state keeps the request visibly pending until the nodes are READY to
+  // take.
+  SliceReadbackFn<PFSPNode> serve_extract;
+  if (extract)
+    serve_extract = [extract, m](const SliceReadback<PFSPNode>& rb) {
+      extract->live_size.store(rb.hc->size, std::memory_order_relaxed);
+      int want = ExtractShare::WANTED;
+      if (extract->state.load(std::memory_order_relaxed) == want &&
+          rb.hc->size >= 2 * static_cast<unsigned long long>(m) &&
+          extract->state.compare_exchange_strong(want, ExtractShare::CARVING,
+                                                 std::memory_order_acq_rel)) {
+        const unsigned long long before = rb.hc->size;
+        carve_back_half(rb, &extract->mu, [extract](unsigned long long half) {
+          extract->taken.resize(half);
+          return extract->taken.data();
+        });
+        if (std::getenv("GATS_CARVE_LOG"))
+          fprintf(stderr, "CARVE pool=%p size %llu -> %llu tree=%llu iters=%llu\n",
+                  (void*)rb.pool_d, before, rb.hc->size, rb.hc->tree, rb.hc->iters);
+        extract->state.store(ExtractShare::READY, std::memory_order_release);
+      }
+    };
+  // deep-frontier rule: 12+ open jobs
+  return devpool_multi(PfspDevProblem(I, lbg), pool, devpool_slices(lbg),
+                       /*deep_levels=*/12, best0, m, M, devices, capacity,
+                       shared_best ? shared_best : &local_best, r, serve_extract);
 }
 
 // ---------------------------------------------------------------------------
@@ -1451,8 +1214,7 @@ Result pfsp_gpu_run(const PfspInstance& I, LbKind lb, Pool<PFSPNode>& pool, int 
 
 // Host-side instance (Taillard matrix + lb1/lb2 tables incl. 190 Johnson
 // sorts) cached per (inst, ub, branching rule).
-static const PfspInstance& pfsp_instance_cached(int inst, int ub,
-                                                Branching br = Branching::FWD) {
+const PfspInstance& pfsp_instance_cached(int inst, int ub, Branching br) {
   static std::mutex mu;
   static std::map<std::pair<std::pair<int, int>, int>, PfspInstance*> cache;
   std::lock_guard<std::mutex> l(mu);
@@ -1561,548 +1323,77 @@ Result pfsp_gpu_from_pool(const std::vector<PFSPNode>& nodes, int inst,
 // Device-built frontiers (declared in engine_gpu.hpp)
 // ---------------------------------------------------------------------------
 
-std::vector<NQNode> nq_gpu_frontier(int N, int g, size_t target, int device,
-                                    uint64_t& tree, uint64_t& sol) {
+// Expands `root` level by level until the pool holds `target` nodes; returns
+// the pool and, in `fin`, the final control block.
+template <class Problem>
+static std::vector<typename Problem::Node> gpu_frontier(const Problem& problem,
+                                                        const typename Problem::Node& root,
+                                                        size_t target, int device, int best0,
+                                                        DevCtl& fin) {
+  using NodeT = typename Problem::Node;
   set_device_cached(device);
+  const Problem P = problem.on_device(device);
   StreamGuard stream;
   Result r;
   const unsigned long long M = target;  // one level per iteration below target
   const unsigned long long capacity = target * (MAX_JOBS + 1) + 64;  // branching <= 20
-  DevGuard<NQNode> pool_d(capacity);
-  DevGuard<DevCtl> ctl_d(2);
-  const int G = devpool_grid(M, N, 1);
-  const int stride = devpool_stride(1);
-  DevGuard<NQNode> childbuf_d(static_cast<size_t>(G) * stride);
-  DevGuard<uint32_t> bc_d(G);
-  DevGuard<unsigned long long> bs_d(G), be_d(G);
-  int finish = 8;
-  if (const char* e = std::getenv("GATS_NQ_FINISH")) finish = atoi(e);
-  if (finish > 8) finish = 8;
-  const DevIterBufs<NQNode> bufs{pool_d.p, childbuf_d.p, bc_d.p, bs_d.p,
-                                 be_d.p,   nullptr,      stride, capacity};
+  const bool presum = (P.lbg == 2);
+  const DevpoolBufs<NodeT> bufs(capacity, M, P.per, P.lbg, Problem::needs_be, presum);
 
-  NQNode root = nq_root();
   DevCtl ctl{};
   ctl.size = 1;
-  HIP_CHECK(hipMemcpyAsync(pool_d.p, &root, sizeof(NQNode), hipMemcpyHostToDevice, stream.s));
-  HIP_CHECK(hipMemcpyAsync(ctl_d.p, &ctl, sizeof(DevCtl), hipMemcpyHostToDevice, stream.s));
-  HIP_CHECK(hipMemcpyAsync(ctl_d.p + 1, &ctl, sizeof(DevCtl), hipMemcpyHostToDevice, stream.s));
-  HIP_CHECK(hipStreamSynchronize(stream.s));
+  ctl.best = best0;
+  HIP_CHECK(hipMemcpyAsync(bufs.pool.p, &root, sizeof(NodeT), hipMemcpyHostToDevice, stream.s));
+  upload_ctl_pair(bufs.ctl.p, ctl, stream.s);
 
   auto iter = [&](int parity, unsigned long long bound) {
     const unsigned long long Mi =
         std::min<unsigned long long>(M, std::max<unsigned long long>(bound, 1));
-    enqueue_nq_iter(bufs, ctl_d.p + parity, ctl_d.p + (1 - parity), N, g, finish, 1, Mi,
-                    /*presum=*/false, stream.s);
+    P.enqueue(bufs, bufs.ctl.p + parity, bufs.ctl.p + (1 - parity), 1, Mi, presum, stream.s);
   };
   DevLoopCfg cfg;
   cfg.m = 1;
   cfg.init_size = 1;
   cfg.stop_size = target;
-  cfg.per = N;
+  cfg.per = P.per;
   cfg.allow_graph = false;
-  const DevCtl fin = run_devpool_loop(stream.s, ctl_d.p, cfg, iter, r);
-  tree = fin.tree;
-  sol = fin.sol;
-  std::vector<NQNode> nodes(fin.size);
+  fin = run_devpool_loop(stream.s, bufs.ctl.p, cfg, iter, r);
+  std::vector<NodeT> nodes(fin.size);
   if (fin.size > 0) {
     // staged through cached pinned memory: a pageable 7 MB D2H runs ~5x
     // slower and showed up as ~10 ms/step in the bench
-    PinnedGuard<NQNode> stage(capacity);
-    HIP_CHECK(hipMemcpyAsync(stage.p, pool_d.p, fin.size * sizeof(NQNode),
+    PinnedGuard<NodeT> stage(capacity);
+    HIP_CHECK(hipMemcpyAsync(stage.p, bufs.pool.p, fin.size * sizeof(NodeT),
                              hipMemcpyDeviceToHost, stream.s));
     HIP_CHECK(hipStreamSynchronize(stream.s));
-    std::memcpy(nodes.data(), stage.p, fin.size * sizeof(NQNode));
+    std::memcpy(nodes.data(), stage.p, fin.size * sizeof(NodeT));
   }
+  return nodes;
+}
+
+std::vector<NQNode> nq_gpu_frontier(int N, int g, size_t target, int device,
+                                    uint64_t& tree, uint64_t& sol) {
+  DevCtl fin;
+  std::vector<NQNode> nodes = gpu_frontier(NqDevProblem(N, g, nq_finish_depth()), nq_root(),
+                                           target, device, /*best0=*/0, fin);
+  tree = fin.tree;
+  sol = fin.sol;
   return nodes;
 }
 
 std::vector<PFSPNode> pfsp_gpu_frontier(const PfspInstance& I, int lbk, size_t target,
                                         int device, int best0, uint64_t& tree,
                                         uint64_t& sol, int& best_out) {
-  if (I.br != Branching::FWD && lbk != 0)
-    throw std::invalid_argument(std::string("branching rule '") + branching_name(I.br) +
-                                "' on the gpu tier needs lb1_d");
-  set_device_cached(device);
-  const PfspDevTables& tb = pfsp_tables_cached(I, device);
-  StreamGuard stream;
-  Result r;
-  const int jobs = I.jobs, machines = I.machines;
-  const int lbg = devpool_lbk_geom(lbk, machines);
-  const unsigned long long M = target;
-  const unsigned long long capacity = target * (MAX_JOBS + 1) + 64;
-  DevGuard<PFSPNode> pool_d(capacity);
-  DevGuard<DevCtl> ctl_d(2);
-  const int G = devpool_grid(M, jobs, lbg);
-  const int stride = devpool_stride(lbg);
-  DevGuard<PFSPNode> childbuf_d(static_cast<size_t>(G) * stride);
-  DevGuard<uint32_t> bc_d(G);
-  DevGuard<unsigned long long> bs_d(G);
-  const bool presum = (lbg == 2);
-  DevGuard<uint32_t> gsum_d(presum ? (G + 255) / 256 : 1);
-  const DevIterBufs<PFSPNode> bufs{pool_d.p, childbuf_d.p, bc_d.p,  bs_d.p,
-                                   nullptr,  gsum_d.p,     stride, capacity};
-
-  PFSPNode root = pfsp_root();
-  DevCtl ctl{};
-  ctl.size = 1;
-  ctl.best = best0;
-  HIP_CHECK(hipMemcpyAsync(pool_d.p, &root, sizeof(PFSPNode), hipMemcpyHostToDevice,
-                           stream.s));
-  HIP_CHECK(hipMemcpyAsync(ctl_d.p, &ctl, sizeof(DevCtl), hipMemcpyHostToDevice, stream.s));
-  HIP_CHECK(hipMemcpyAsync(ctl_d.p + 1, &ctl, sizeof(DevCtl), hipMemcpyHostToDevice, stream.s));
-  HIP_CHECK(hipStreamSynchronize(stream.s));
-
-  auto iter = [&](int parity, unsigned long long bound) {
-    const unsigned long long Mi =
-        std::min<unsigned long long>(M, std::max<unsigned long long>(bound, 1));
-    enqueue_pfsp_iter(bufs, ctl_d.p + parity, ctl_d.p + (1 - parity), jobs, machines, lbg, tb,
-                      1, Mi, presum, stream.s, static_cast<int>(I.br));
-  };
-  DevLoopCfg cfg;
-  cfg.m = 1;
-  cfg.init_size = 1;
-  cfg.stop_size = target;
-  cfg.per = jobs;
-  cfg.allow_graph = false;
-  const DevCtl fin = run_devpool_loop(stream.s, ctl_d.p, cfg, iter, r);
+  check_devpool_branching(I, lbk);
+  DevCtl fin;
+  std::vector<PFSPNode> nodes =
+      gpu_frontier(PfspDevProblem(I, devpool_lbk_geom(lbk, I.machines)), pfsp_root(), target,
+                   device, best0, fin);
   tree = fin.tree;
   sol = fin.sol;
   best_out = fin.best;
-  std::vector<PFSPNode> nodes(fin.size);
-  if (fin.size > 0) {
-    PinnedGuard<PFSPNode> stage(capacity);
-    HIP_CHECK(hipMemcpyAsync(stage.p, pool_d.p, fin.size * sizeof(PFSPNode),
-                             hipMemcpyDeviceToHost, stream.s));
-    HIP_CHECK(hipStreamSynchronize(stream.s));
-    std::memcpy(nodes.data(), stage.p, fin.size * sizeof(PFSPNode));
-  }
   return nodes;
 }
-
-// ---------------------------------------------------------------------------
-// Single-iteration entry points (declared in engine_gpu.hpp): upload a chosen
-// pool, run exactly ONE devpool iteration through enqueue_*_iter, read the
-// pool and the next control block back. The step tests compare every byte
-// and counter with a CPU oracle.
-// ---------------------------------------------------------------------------
-
-namespace {
-
-int presum_mode(const std::string& presum) {
-  if (presum == "auto") return -1;
-  if (presum == "on") return 1;
-  if (presum == "off") return 0;
-  throw std::invalid_argument("presum must be 'auto', 'on' or 'off'");
-}
-
-void validate_step_window(size_t n, int per, unsigned long long m, unsigned long long M,
-                          unsigned long long capacity) {
-  if (m < 1) throw std::invalid_argument("m must be >= 1");
-  if (M < 1) throw std::invalid_argument("M must be >= 1");
-  if (M > (1ull << 31) / static_cast<unsigned long long>(per))
-    throw std::invalid_argument("M * branching must be <= 2^31");
-  if (capacity < n) throw std::invalid_argument("capacity must be >= the number of nodes");
-}
-
-template <class NodeT>
-DevpoolStepCtl step_readback(std::vector<NodeT>& nodes, const NodeT* pool_d,
-                             const DevCtl* ctl_next_d, unsigned long long capacity,
-                             hipStream_t s) {
-  DevCtl fin{};
-  HIP_CHECK(hipMemcpyAsync(&fin, ctl_next_d, sizeof(DevCtl), hipMemcpyDeviceToHost, s));
-  HIP_CHECK(hipStreamSynchronize(s));
-  if (fin.size > capacity) throw std::runtime_error("devpool step: size exceeds capacity");
-  nodes.resize(fin.size);
-  if (fin.size > 0) {
-    HIP_CHECK(hipMemcpyAsync(nodes.data(), pool_d, fin.size * sizeof(NodeT),
-                             hipMemcpyDeviceToHost, s));
-    HIP_CHECK(hipStreamSynchronize(s));
-  }
-  return {fin.size, fin.chunk, fin.tree, fin.sol, fin.iters, fin.best, fin.overflow};
-}
-
-}  // namespace
-
-void validate_nq_step(const std::vector<NQNode>& nodes, int N, int g, int finish,
-                      unsigned long long m, unsigned long long M,
-                      unsigned long long capacity, const std::string& presum) {
-  // the expand kernel stages EMIT_TILE / 4 + 2 parents per block: N >= 4
-  if (N < 4 || N > MAX_JOBS) throw std::invalid_argument("N must be in 4..20");
-  if (g < 1) throw std::invalid_argument("g must be >= 1");
-  if (finish < -1 || finish > 8) throw std::invalid_argument("finish must be in -1..8");
-  validate_step_window(nodes.size(), N, m, M, capacity);
-  presum_mode(presum);
-  for (size_t i = 0; i < nodes.size(); i++) {
-    const NQNode& p = nodes[i];
-    if (p.depth > N)
-      throw std::invalid_argument("node " + std::to_string(i) + ": depth > N");
-    uint32_t seen = 0;
-    for (int j = 0; j < N; j++) {
-      if (p.board[j] >= N || (seen >> p.board[j] & 1u))
-        throw std::invalid_argument("node " + std::to_string(i) +
-                                    ": board[0:N] is not a permutation of 0..N-1");
-      seen |= 1u << p.board[j];
-    }
-  }
-}
-
-void validate_pfsp_step(const std::vector<PFSPNode>& nodes, int inst, const std::string& lb,
-                        unsigned long long m, unsigned long long M,
-                        unsigned long long capacity, int geom, const std::string& presum,
-                        const std::string& br_str) {
-  const LbKind lbk = lb_from_string(lb);
-  const Branching br = branching_from_string(br_str);
-  check_branching_supported(lbk, br, true);
-  const int jobs = taillard_nb_jobs(inst);
-  if (jobs > MAX_JOBS)
-    throw std::invalid_argument("instance exceeds MAX_JOBS=20 (use ta001..ta030)");
-  if (geom != -1 && geom != 2 && geom != 3)
-    throw std::invalid_argument("geom must be -1, 2 or 3");
-  if (geom != -1 && lbk != LbKind::LB2)
-    throw std::invalid_argument("geom 2/3 select an lb2 kernel: lb must be 'lb2'");
-  validate_step_window(nodes.size(), jobs, m, M, capacity);
-  presum_mode(presum);
-  for (size_t i = 0; i < nodes.size(); i++) {
-    const PFSPNode& p = nodes[i];
-    if (p.depth < 0 || p.depth > jobs - 1)
-      throw std::invalid_argument("node " + std::to_string(i) + ": depth not in 0..jobs-1");
-    if (br == Branching::FWD) {
-      // the forward kernels take limit2 == jobs for granted
-      if (p.limit1 != p.depth - 1)
-        throw std::invalid_argument("node " + std::to_string(i) + ": limit1 != depth - 1");
-      if (p.nback != 0)
-        throw std::invalid_argument("node " + std::to_string(i) +
-                                    ": nback != 0 needs a non-fwd branching rule");
-    } else if (p.limit1 < -1 || p.limit1 + 1 + static_cast<int>(p.nback) != p.depth) {
-      throw std::invalid_argument("node " + std::to_string(i) +
-                                  ": depth != limit1 + 1 + nback");
-    }
-    uint32_t seen = 0;
-    for (int j = 0; j < jobs; j++) {
-      if (p.prmu[j] >= jobs || (seen >> p.prmu[j] & 1u))
-        throw std::invalid_argument("node " + std::to_string(i) +
-                                    ": prmu[0:jobs] is not a permutation of 0..jobs-1");
-      seen |= 1u << p.prmu[j];
-    }
-  }
-}
-
-DevpoolStepCtl nq_devpool_step(std::vector<NQNode>& nodes, int N, int g, int finish,
-                               unsigned long long m, unsigned long long M,
-                               unsigned long long capacity, const std::string& presum,
-                               int device) {
-  validate_nq_step(nodes, N, g, finish, m, M, capacity, presum);  // before any HIP call
-  const int pm = presum_mode(presum);
-  const size_t n = nodes.size();
-  // grids sized to the pool that exists, like the engine loops' chunk bound
-  // (bound >= size, so min(size, Mi) == min(size, M))
-  const unsigned long long Mi = std::min<unsigned long long>(M, std::max<size_t>(n, 1));
-  set_device_cached(device);
-  StreamGuard stream;
-  DevGuard<NQNode> pool_d(std::max<unsigned long long>(capacity, 1));
-  DevGuard<DevCtl> ctl_d(2);
-  const int G = devpool_grid(Mi, N, 1);
-  const int stride = devpool_stride(1);
-  DevGuard<NQNode> childbuf_d(static_cast<size_t>(G) * stride);
-  DevGuard<uint32_t> bc_d(G);
-  DevGuard<unsigned long long> bs_d(G), be_d(G);
-  DevGuard<uint32_t> gsum_d((G + 255) / 256);
-  const bool ps = pm < 0 ? G > 1024 : pm == 1;  // auto: devpool_thread_nq's rule
-  const DevIterBufs<NQNode> bufs{pool_d.p, childbuf_d.p, bc_d.p,  bs_d.p,
-                                 be_d.p,   gsum_d.p,     stride, capacity};
-  DevCtl ctl{};
-  ctl.size = n;
-  if (n > 0)
-    HIP_CHECK(hipMemcpyAsync(pool_d.p, nodes.data(), n * sizeof(NQNode),
-                             hipMemcpyHostToDevice, stream.s));
-  HIP_CHECK(hipMemcpyAsync(ctl_d.p, &ctl, sizeof(DevCtl), hipMemcpyHostToDevice, stream.s));
-  HIP_CHECK(hipMemcpyAsync(ctl_d.p + 1, &ctl, sizeof(DevCtl), hipMemcpyHostToDevice, stream.s));
-  HIP_CHECK(hipStreamSynchronize(stream.s));
-  enqueue_nq_iter(bufs, ctl_d.p, ctl_d.p + 1, N, g, finish, m, Mi, ps, stream.s);
-  HIP_CHECK(hipGetLastError());
-  return step_readback(nodes, pool_d.p, ctl_d.p + 1, capacity, stream.s);
-}
-
-DevpoolStepCtl pfsp_devpool_step(std::vector<PFSPNode>& nodes, int inst, const std::string& lb,
-                                 int best, unsigned long long m, unsigned long long M,
-                                 unsigned long long capacity, int geom,
-                                 const std::string& presum, int device,
-                                 const std::string& br) {
-  validate_pfsp_step(nodes, inst, lb, m, M, capacity, geom, presum, br);  // before any HIP call
-  const int pm = presum_mode(presum);
-  const PfspInstance& I = pfsp_instance_cached(inst, 1, branching_from_string(br));
-  const int jobs = I.jobs, machines = I.machines;
-  const int lbg = geom < 0 ? devpool_lbk_geom(lbk_of(lb_from_string(lb)), machines) : geom;
-  const size_t n = nodes.size();
-  const unsigned long long Mi = std::min<unsigned long long>(M, std::max<size_t>(n, 1));
-  set_device_cached(device);
-  const PfspDevTables& tb = pfsp_tables_cached(I, device);
-  StreamGuard stream;
-  DevGuard<PFSPNode> pool_d(std::max<unsigned long long>(capacity, 1));
-  DevGuard<DevCtl> ctl_d(2);
-  const int G = devpool_grid(Mi, jobs, lbg);
-  const int stride = devpool_stride(lbg);
-  DevGuard<PFSPNode> childbuf_d(static_cast<size_t>(G) * stride);
-  DevGuard<uint32_t> bc_d(G);
-  DevGuard<unsigned long long> bs_d(G);
-  DevGuard<uint32_t> gsum_d((G + 255) / 256);
-  // auto: devpool_thread_pfsp's rule (pfsp_gpu_frontier's is its lbg == 2 half)
-  const bool ps = pm < 0 ? (lbg == 2 || G > 1024) : pm == 1;
-  const DevIterBufs<PFSPNode> bufs{pool_d.p, childbuf_d.p, bc_d.p,  bs_d.p,
-                                   nullptr,  gsum_d.p,     stride, capacity};
-  DevCtl ctl{};
-  ctl.size = n;
-  ctl.best = best;
-  if (n > 0)
-    HIP_CHECK(hipMemcpyAsync(pool_d.p, nodes.data(), n * sizeof(PFSPNode),
-                             hipMemcpyHostToDevice, stream.s));
-  HIP_CHECK(hipMemcpyAsync(ctl_d.p, &ctl, sizeof(DevCtl), hipMemcpyHostToDevice, stream.s));
-  HIP_CHECK(hipMemcpyAsync(ctl_d.p + 1, &ctl, sizeof(DevCtl), hipMemcpyHostToDevice, stream.s));
-  HIP_CHECK(hipStreamSynchronize(stream.s));
-  enqueue_pfsp_iter(bufs, ctl_d.p, ctl_d.p + 1, jobs, machines, lbg, tb, m, Mi, ps, stream.s,
-                    static_cast<int>(I.br));
-  HIP_CHECK(hipGetLastError());
-  return step_readback(nodes, pool_d.p, ctl_d.p + 1, capacity, stream.s);
-}
-
-// ---------------------------------------------------------------------------
-// Chain entry points (declared in engine_gpu.hpp): k iterations back to back
-// over ONE set of buffers sized for the largest window, alternating control
-// blocks, no host synchronisation in between — the launch shape of the engine
-// threads, minus the loop driver. A snapshot of the live control block and of
-// the pool follows every iteration on the same stream.
-// ---------------------------------------------------------------------------
-
-namespace {
-
-constexpr unsigned long long CHAIN_MAX_ITERS = 16;
-constexpr unsigned long long CHAIN_MAX_NODES = 1ull << 22;  // capacity * (k + 1)
-
-void validate_chain_windows(const std::vector<unsigned long long>& windows, int per,
-                            unsigned long long capacity) {
-  const unsigned long long k = windows.size();
-  if (k < 1 || k > CHAIN_MAX_ITERS)
-    throw std::invalid_argument("windows must hold 1..16 entries");
-  for (unsigned long long w : windows) {
-    if (w < 1) throw std::invalid_argument("every window must be >= 1");
-    if (w > (1ull << 31) / static_cast<unsigned long long>(per))
-      throw std::invalid_argument("window * branching must be <= 2^31");
-  }
-  if (capacity > CHAIN_MAX_NODES / (k + 1))
-    throw std::invalid_argument("capacity * (len(windows) + 1) must be <= 2^22 nodes");
-}
-
-// Snapshot areas + the read-back shared by both problems. `enqueue(i, cur,
-// next)` enqueues iteration i.
-template <class NodeT, class Enqueue>
-std::vector<DevpoolSnapshot<NodeT>> run_chain(const std::vector<NodeT>& nodes, NodeT* pool_d,
-                                              DevCtl* ctl_d, int best,
-                                              const std::vector<unsigned long long>& windows,
-                                              unsigned long long m,
-                                              unsigned long long capacity, hipStream_t s,
-                                              Enqueue enqueue) {
-  const size_t n = nodes.size();
-  const size_t k = windows.size();
-  DevGuard<NodeT> snap_pool_d(std::max<size_t>(capacity * k, 1));
-  DevGuard<DevCtl> snap_ctl_d(k);
-  DevCtl ctl{};
-  ctl.size = n;
-  ctl.best = best;
-  if (n > 0)
-    HIP_CHECK(hipMemcpyAsync(pool_d, nodes.data(), n * sizeof(NodeT), hipMemcpyHostToDevice, s));
-  HIP_CHECK(hipMemcpyAsync(ctl_d, &ctl, sizeof(DevCtl), hipMemcpyHostToDevice, s));
-  HIP_CHECK(hipMemcpyAsync(ctl_d + 1, &ctl, sizeof(DevCtl), hipMemcpyHostToDevice, s));
-  HIP_CHECK(hipStreamSynchronize(s));
-  for (size_t i = 0; i < k; i++) {
-    DevCtl* cur = ctl_d + (i & 1);
-    DevCtl* next = ctl_d + 1 - (i & 1);
-    enqueue(i, cur, next);
-    HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipMemcpyAsync(snap_ctl_d.p + i, next, sizeof(DevCtl), hipMemcpyDeviceToDevice, s));
-    if (capacity > 0)
-      HIP_CHECK(hipMemcpyAsync(snap_pool_d.p + i * capacity, pool_d, capacity * sizeof(NodeT),
-                               hipMemcpyDeviceToDevice, s));
-  }
-  std::vector<DevCtl> fin(k);
-  HIP_CHECK(hipMemcpyAsync(fin.data(), snap_ctl_d.p, k * sizeof(DevCtl), hipMemcpyDeviceToHost, s));
-  HIP_CHECK(hipStreamSynchronize(s));
-
-  std::vector<DevpoolSnapshot<NodeT>> out(k);
-  // live size entering iteration i, and the un-popped prefix once overflowed:
-  // the overflowing iteration leaves [base, ..) undefined and every later
-  // iteration pops nothing, so that prefix is what all later snapshots keep
-  unsigned long long prev = n, ovf_base = 0;
-  bool overflowed = false;
-  for (size_t i = 0; i < k; i++) {
-    const DevCtl& f = fin[i];
-    unsigned long long keep;
-    if (f.overflow) {
-      if (!overflowed) {
-        const unsigned long long c = prev < m ? 0 : std::min(prev, windows[i]);
-        ovf_base = prev - c;
-        overflowed = true;
-      }
-      keep = ovf_base;
-    } else {
-      if (f.size > capacity) throw std::runtime_error("devpool chain: size exceeds capacity");
-      keep = f.size;
-      prev = f.size;
-    }
-    if (keep > capacity) throw std::runtime_error("devpool chain: prefix exceeds capacity");
-    out[i].nodes.resize(keep);
-    if (keep > 0)
-      HIP_CHECK(hipMemcpyAsync(out[i].nodes.data(), snap_pool_d.p + i * capacity,
-                               keep * sizeof(NodeT), hipMemcpyDeviceToHost, s));
-    out[i].ctl = {f.size, f.chunk, f.tree, f.sol, f.iters, f.best, f.overflow};
-  }
-  HIP_CHECK(hipStreamSynchronize(s));
-  return out;
-}
-
-}  // namespace
-
-std::vector<DevpoolSnapshot<NQNode>> nq_devpool_chain(
-    const std::vector<NQNode>& nodes, int N, int g, int finish, unsigned long long m,
-    const std::vector<unsigned long long>& windows, unsigned long long capacity,
-    const std::string& presum, int device) {
-  validate_nq_step(nodes, N, g, finish, m, 1, capacity, presum);  // before any HIP call
-  validate_chain_windows(windows, N, capacity);
-  const int pm = presum_mode(presum);
-  const unsigned long long Mc = *std::max_element(windows.begin(), windows.end());
-  set_device_cached(device);
-  StreamGuard stream;
-  DevGuard<NQNode> pool_d(std::max<unsigned long long>(capacity, 1));
-  DevGuard<DevCtl> ctl_d(2);
-  // sized ONCE for the largest window, as devpool_thread_nq sizes them for Mc
-  const int G = devpool_grid(Mc, N, 1);
-  const int stride = devpool_stride(1);
-  DevGuard<NQNode> childbuf_d(static_cast<size_t>(G) * stride);
-  DevGuard<uint32_t> bc_d(G);
-  DevGuard<unsigned long long> bs_d(G), be_d(G);
-  const bool presum_alloc = devpool_presum_alloc(G, 1);
-  DevGuard<uint32_t> gsum_d((presum_alloc || pm == 1) ? (G + 255) / 256 : 1);
-  const DevIterBufs<NQNode> bufs{pool_d.p, childbuf_d.p, bc_d.p,  bs_d.p,
-                                 be_d.p,   gsum_d.p,     stride, capacity};
-  return run_chain(nodes, pool_d.p, ctl_d.p, 0, windows, m, capacity, stream.s,
-                   [&](size_t i, DevCtl* cur, DevCtl* next) {
-                     const DevIterPolicy it =
-                         devpool_iter_policy(Mc, windows[i], N, 1, presum_alloc);
-                     const bool ps = pm < 0 ? it.ps : pm == 1;
-                     enqueue_nq_iter(bufs, cur, next, N, g, finish, m, it.Mi, ps, stream.s);
-                   });
-}
-
-std::vector<DevpoolSnapshot<PFSPNode>> pfsp_devpool_chain(
-    const std::vector<PFSPNode>& nodes, int inst, const std::string& lb, int best,
-    unsigned long long m, const std::vector<unsigned long long>& windows,
-    unsigned long long capacity, int geom, const std::string& presum, int device,
-    const std::string& br) {
-  validate_pfsp_step(nodes, inst, lb, m, 1, capacity, geom, presum, br);  // before any HIP call
-  validate_chain_windows(windows, taillard_nb_jobs(inst), capacity);
-  const int pm = presum_mode(presum);
-  const PfspInstance& I = pfsp_instance_cached(inst, 1, branching_from_string(br));
-  const int jobs = I.jobs, machines = I.machines;
-  const int lbg = geom < 0 ? devpool_lbk_geom(lbk_of(lb_from_string(lb)), machines) : geom;
-  const unsigned long long Mc = *std::max_element(windows.begin(), windows.end());
-  set_device_cached(device);
-  const PfspDevTables& tb = pfsp_tables_cached(I, device);
-  StreamGuard stream;
-  DevGuard<PFSPNode> pool_d(std::max<unsigned long long>(capacity, 1));
-  DevGuard<DevCtl> ctl_d(2);
-  // sized ONCE for the largest window, as devpool_thread_pfsp sizes them for Mc
-  const int G = devpool_grid(Mc, jobs, lbg);
-  const int stride = devpool_stride(lbg);
-  DevGuard<PFSPNode> childbuf_d(static_cast<size_t>(G) * stride);
-  DevGuard<uint32_t> bc_d(G);
-  DevGuard<unsigned long long> bs_d(G);
-  const bool presum_alloc = devpool_presum_alloc(G, lbg);
-  DevGuard<uint32_t> gsum_d((presum_alloc || pm == 1) ? (G + 255) / 256 : 1);
-  const DevIterBufs<PFSPNode> bufs{pool_d.p, childbuf_d.p, bc_d.p,  bs_d.p,
-                                   nullptr,  gsum_d.p,     stride, capacity};
-  return run_chain(nodes, pool_d.p, ctl_d.p, best, windows, m, capacity, stream.s,
-                   [&](size_t i, DevCtl* cur, DevCtl* next) {
-                     const DevIterPolicy it =
-                         devpool_iter_policy(Mc, windows[i], jobs, lbg, presum_alloc);
-                     const bool ps = pm < 0 ? it.ps : pm == 1;
-                     enqueue_pfsp_iter(bufs, cur, next, jobs, machines, lbg, tb, m, it.Mi, ps,
-                                       stream.s, static_cast<int>(I.br));
-                   });
-}
-
-// ---------------------------------------------------------------------------
-// Eval-only entry points (HIP-kernel-vs-CPU-oracle numerics tests)
-// ---------------------------------------------------------------------------
-
-std::vector<uint8_t> nq_gpu_labels(int N, int g, const std::vector<NQNode>& nodes,
-                                   int device) {
-  set_device_cached(device);
-  const size_t n = nodes.size();
-  std::vector<uint8_t> labels(n * N, 255);
-  DevGuard<NQNode> parents_d(n);
-  DevGuard<uint8_t> labels_d(n * N);
-  HIP_CHECK(hipMemcpy(parents_d.p, nodes.data(), n * sizeof(NQNode), hipMemcpyHostToDevice));
-  HIP_CHECK(hipMemset(labels_d.p, 255, n * N));
-  launch_nq_eval(parents_d.p, static_cast<int>(n), N, g, labels_d.p, nullptr);
-  HIP_CHECK(hipMemcpy(labels.data(), labels_d.p, n * N, hipMemcpyDeviceToHost));
-  return labels;
-}
-
-std::vector<int32_t> pfsp_gpu_bounds(int inst, const std::string& lb_str,
-                                     const std::vector<PFSPNode>& nodes, int best,
-                                     int device) {
-  const LbKind lb = lb_from_string(lb_str);
-  PfspInstance I = make_pfsp_instance(inst, 1);
-  set_device_cached(device);
-  PfspTablesGuard tables(I);
-  const size_t n = nodes.size();
-  std::vector<int32_t> bounds(n * I.jobs, -1);
-  DevGuard<PFSPNode> parents_d(n);
-  DevGuard<int32_t> bounds_d(n * I.jobs);
-  HIP_CHECK(hipMemcpy(parents_d.p, nodes.data(), n * sizeof(PFSPNode), hipMemcpyHostToDevice));
-  HIP_CHECK(hipMemset(bounds_d.p, 255, n * I.jobs * sizeof(int32_t)));
-  launch_pfsp_eval(parents_d.p, static_cast<int>(n), I.jobs, I.machines, lbk_of(lb),
-                   tables.tb, best, bounds_d.p, nullptr);
-  HIP_CHECK(hipMemcpy(bounds.data(), bounds_d.p, n * I.jobs * sizeof(int32_t),
-                      hipMemcpyDeviceToHost));
-  return bounds;
-}
-
-
-std::pair<std::vector<int32_t>, std::vector<int32_t>> pfsp_gpu_bounds_bi(
-    int inst, const std::vector<PFSPNode>& nodes, int device) {
-  PfspInstance I = make_pfsp_instance(inst, 1);
-  // the kernel indexes prmu by [limit1 + 1, jobs - nback): check before any HIP call
-  for (size_t i = 0; i < nodes.size(); i++) {
-    const PFSPNode& p = nodes[i];
-    if (p.limit1 < -1 || p.limit1 + 1 + static_cast<int>(p.nback) > I.jobs)
-      throw std::invalid_argument("node " + std::to_string(i) +
-                                  ": limit1 + 1 + nback exceeds jobs");
-    for (int j = 0; j < I.jobs; j++)
-      if (p.prmu[j] >= I.jobs)
-        throw std::invalid_argument("node " + std::to_string(i) + ": prmu entry >= jobs");
-  }
-  set_device_cached(device);
-  PfspTablesGuard tables(I);
-  const size_t n = nodes.size();
-  std::vector<int32_t> lb_begin(n * I.jobs, -1), lb_end(n * I.jobs, -1);
-  if (n == 0) return {lb_begin, lb_end};
-  DevGuard<PFSPNode> parents_d(n);
-  DevGuard<int32_t> begin_d(n * I.jobs), end_d(n * I.jobs);
-  HIP_CHECK(hipMemcpy(parents_d.p, nodes.data(), n * sizeof(PFSPNode), hipMemcpyHostToDevice));
-  HIP_CHECK(hipMemset(begin_d.p, 255, n * I.jobs * sizeof(int32_t)));
-  HIP_CHECK(hipMemset(end_d.p, 255, n * I.jobs * sizeof(int32_t)));
-  (void)hipGetLastError();  // drop a stale launch error of an earlier, unchecked call
-  launch_pfsp_eval(parents_d.p, static_cast<int>(n), I.jobs, I.machines, 0, tables.tb, 0,
-                   begin_d.p, nullptr, static_cast<int>(Branching::MINBRANCH), end_d.p);
-  HIP_CHECK(hipGetLastError());
-  HIP_CHECK(hipMemcpy(lb_begin.data(), begin_d.p, n * I.jobs * sizeof(int32_t),
-                      hipMemcpyDeviceToHost));
-  HIP_CHECK(hipMemcpy(lb_end.data(), end_d.p, n * I.jobs * sizeof(int32_t),
-                      hipMemcpyDeviceToHost));
-  return {lb_begin, lb_end};
-}
-
 
 // ---------------------------------------------------------------------------
 // Asynchronous PFSP engine: runs the devpool search on a background thread
@@ -2164,12 +1455,7 @@ void PfspAsyncEngine::loop() {
       if (r.optimum > 0 &&
           (result_.optimum == 0 || r.optimum < result_.optimum))
         result_.optimum = r.optimum;
-      result_.kernel_launch += r.kernel_launch;
-      result_.h2d += r.h2d;
-      result_.d2h += r.d2h;
-      result_.h2d_bytes += r.h2d_bytes;
-      result_.d2h_bytes += r.d2h_bytes;
-      result_.gpu_iters += r.gpu_iters;
+      merge_slice_diag(result_, r);
       {
         std::lock_guard<std::mutex> l(mu_);
         running_ = false;

@@ -1,4 +1,5 @@
-// Public API of the single-GPU engines (implemented in engine_gpu.cpp).
+// Public API of the single-GPU engines (implemented in engine_gpu.cpp; the
+// test-only entry points at the end in engine_testing.cpp).
 #pragma once
 #include <atomic>
 #include <condition_variable>
@@ -217,7 +218,7 @@ DevpoolStepCtl pfsp_devpool_step(std::vector<PFSPNode>& nodes, int inst, const s
 // validation, with `windows` (1..16 per-iteration launch windows) in place of
 // M. The count / sol / extra / group-sum / child buffers are allocated ONCE
 // for max(windows), as an engine thread sizes them for its chunk cap, and
-// iteration i runs enqueue_*_iter(ctl + (i & 1) -> ctl + 1 - (i & 1)) with
+// iteration i runs one enqueue (ctl + (i & 1) -> ctl + 1 - (i & 1)) with
 // window windows[i] on one stream with no host synchronisation in between.
 // After every iteration the live control block and pool[0:capacity] are
 // copied device-to-device into a snapshot area; snapshot i is (the first
@@ -225,7 +226,7 @@ DevpoolStepCtl pfsp_devpool_step(std::vector<PFSPNode>& nodes, int inst, const s
 // snapshot's overflow flag is set its nodes are the un-popped prefix of the
 // overflowing iteration (all that is defined from then on). presum "auto" is
 // the engine threads' own per-iteration rule (the shared policy helper in
-// engine_gpu.cpp, with the buffers' presum sizing taken from max(windows));
+// engine_internal.hpp, with the buffers' presum sizing taken from max(windows));
 // "on" / "off" force the groupSums pointer present / null every iteration.
 // A window below the pool size is legal and is that iteration's pop cap.
 // Everything is validated on the host before the first HIP call:

@@ -29,20 +29,13 @@
 #include <vector>
 
 #include "engine_gpu.hpp"
+#include "engine_internal.hpp"
 #include "gpu_api.hpp"
 #include "search_host.hpp"
 
 namespace gats {
 
 namespace {
-
-#define HIP_CHECK_M(expr)                                                            \
-  do {                                                                               \
-    hipError_t _e = (expr);                                                          \
-    if (_e != hipSuccess)                                                            \
-      throw std::runtime_error(std::string("HIP error: ") + hipGetErrorString(_e) +  \
-                               " at " #expr);                                        \
-  } while (0)
 
 constexpr bool BUSY = false;
 constexpr bool IDLE = true;
@@ -157,11 +150,11 @@ struct NqGpuCtx {
   int N, g, M;
   NqGpuCtx(int device, int N_, int g_, int M_) : N(N_), g(g_), M(M_) {
     set_device_cached(device);
-    HIP_CHECK_M(hipStreamCreate(&stream));
-    HIP_CHECK_M(hipHostMalloc(reinterpret_cast<void**>(&parents_h), M * sizeof(NQNode)));
-    HIP_CHECK_M(hipHostMalloc(reinterpret_cast<void**>(&labels_h), size_t(M) * N));
-    HIP_CHECK_M(hipMalloc(reinterpret_cast<void**>(&parents_d), M * sizeof(NQNode)));
-    HIP_CHECK_M(hipMalloc(reinterpret_cast<void**>(&labels_d), size_t(M) * N));
+    HIP_CHECK(hipStreamCreate(&stream));
+    HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&parents_h), M * sizeof(NQNode)));
+    HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&labels_h), size_t(M) * N));
+    HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&parents_d), M * sizeof(NQNode)));
+    HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&labels_d), size_t(M) * N));
   }
   ~NqGpuCtx() {
     (void)hipStreamDestroy(stream);
@@ -184,8 +177,8 @@ struct PfspGpuCtx {
   template <typename T>
   T* upload(const std::vector<T>& v) {
     void* p = nullptr;
-    HIP_CHECK_M(hipMalloc(&p, v.size() * sizeof(T)));
-    HIP_CHECK_M(hipMemcpy(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
+    HIP_CHECK(hipMalloc(&p, v.size() * sizeof(T)));
+    HIP_CHECK(hipMemcpy(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
     tb_allocs.push_back(p);
     return static_cast<T*>(p);
   }
@@ -193,8 +186,8 @@ struct PfspGpuCtx {
   template <typename T>
   T* upload_n(const T* src, size_t nelem) {
     void* p = nullptr;
-    HIP_CHECK_M(hipMalloc(&p, nelem * sizeof(T)));
-    HIP_CHECK_M(hipMemcpy(p, src, nelem * sizeof(T), hipMemcpyHostToDevice));
+    HIP_CHECK(hipMalloc(&p, nelem * sizeof(T)));
+    HIP_CHECK(hipMemcpy(p, src, nelem * sizeof(T), hipMemcpyHostToDevice));
     tb_allocs.push_back(p);
     return static_cast<T*>(p);
   }
@@ -202,11 +195,11 @@ struct PfspGpuCtx {
   PfspGpuCtx(int device, const PfspInstance& I, int M_)
       : jobs(I.jobs), machines(I.machines), M(M_) {
     set_device_cached(device);
-    HIP_CHECK_M(hipStreamCreate(&stream));
-    HIP_CHECK_M(hipMalloc(reinterpret_cast<void**>(&parents_d), M * sizeof(PFSPNode)));
-    HIP_CHECK_M(hipMalloc(reinterpret_cast<void**>(&bounds_d),
+    HIP_CHECK(hipStreamCreate(&stream));
+    HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&parents_d), M * sizeof(PFSPNode)));
+    HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&bounds_d),
                           size_t(M) * jobs * sizeof(int32_t)));
-    HIP_CHECK_M(hipHostMalloc(reinterpret_cast<void**>(&bounds_h),
+    HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&bounds_h),
                               size_t(M) * jobs * sizeof(int32_t)));
     std::vector<int16_t> p16(I.lb1.p_times.begin(), I.lb1.p_times.end());
     std::vector<int32_t> mt(I.lb1.min_tails.begin(), I.lb1.min_tails.end());
@@ -295,7 +288,7 @@ static Result pfsp_multigpu_devpool(int inst, const std::string& lb_str, int ub,
   if (ndev == 0) throw std::runtime_error("no HIP device visible");
   std::vector<int> devices(D);
   for (int d = 0; d < D; d++) devices[d] = d % ndev;
-  const int lbk = (lb == LbKind::LB1_D) ? 0 : (lb == LbKind::LB1 ? 1 : 2);
+  const int lbk = lbk_of(lb);
   const double t2 = now_sec();
   DevpoolMultiOut o =
       pfsp_devpool_multi(I, pool, lbk, best, m, M, devices, capacity, nullptr, r);
@@ -355,13 +348,13 @@ Result nqueens_multigpu(int N, int g, int m, int M, int D, const std::string& ev
               id, D, m, M, perc, pools, states, all_idle_flag,
               [&](const NQNode* parents, size_t n, ParPool<NQNode>& own, WorkerDiag& dg) {
                 std::memcpy(ctx.parents_h, parents, n * sizeof(NQNode));
-                HIP_CHECK_M(hipMemcpyAsync(ctx.parents_d, ctx.parents_h, n * sizeof(NQNode),
+                HIP_CHECK(hipMemcpyAsync(ctx.parents_d, ctx.parents_h, n * sizeof(NQNode),
                                            hipMemcpyHostToDevice, ctx.stream));
                 launch_nq_eval(ctx.parents_d, static_cast<int>(n), N, g, ctx.labels_d,
                                ctx.stream);
-                HIP_CHECK_M(hipMemcpyAsync(ctx.labels_h, ctx.labels_d, n * N,
+                HIP_CHECK(hipMemcpyAsync(ctx.labels_h, ctx.labels_d, n * N,
                                            hipMemcpyDeviceToHost, ctx.stream));
-                HIP_CHECK_M(hipStreamSynchronize(ctx.stream));
+                HIP_CHECK(hipStreamSynchronize(ctx.stream));
                 dg.kernel_launch++;
                 dg.h2d++;
                 dg.d2h++;
@@ -461,7 +454,7 @@ Result pfsp_multigpu(int inst, const std::string& lb_str, int ub, int m, int M, 
 
   const int ndev = (eval == "gpu") ? gpu_device_count() : 0;
   if (eval == "gpu" && ndev == 0) throw std::runtime_error("no HIP device visible");
-  const int lbk = (lb == LbKind::LB1_D) ? 0 : (lb == LbKind::LB1 ? 1 : 2);
+  const int lbk = lbk_of(lb);
 
   const double t2 = now_sec();
   for (int id = 0; id < D; id++) {
@@ -490,21 +483,21 @@ Result pfsp_multigpu(int inst, const std::string& lb_str, int ub, int m, int M, 
         if (eval == "gpu") {
           PfspGpuCtx ctx(id % ndev, I, M);
           PFSPNode* parents_h = nullptr;
-          HIP_CHECK_M(
+          HIP_CHECK(
               hipHostMalloc(reinterpret_cast<void**>(&parents_h), M * sizeof(PFSPNode)));
           ws_worker<PFSPNode>(
               id, D, m, M, perc, pools, states, all_idle_flag,
               [&](const PFSPNode* parents, size_t n, ParPool<PFSPNode>& own,
                   WorkerDiag& dg) {
                 std::memcpy(parents_h, parents, n * sizeof(PFSPNode));
-                HIP_CHECK_M(hipMemcpyAsync(ctx.parents_d, parents_h, n * sizeof(PFSPNode),
+                HIP_CHECK(hipMemcpyAsync(ctx.parents_d, parents_h, n * sizeof(PFSPNode),
                                            hipMemcpyHostToDevice, ctx.stream));
                 launch_pfsp_eval(ctx.parents_d, static_cast<int>(n), I.jobs, I.machines,
                                  lbk, ctx.tb, best_l, ctx.bounds_d, ctx.stream);
-                HIP_CHECK_M(hipMemcpyAsync(ctx.bounds_h, ctx.bounds_d,
+                HIP_CHECK(hipMemcpyAsync(ctx.bounds_h, ctx.bounds_d,
                                            n * I.jobs * sizeof(int32_t),
                                            hipMemcpyDeviceToHost, ctx.stream));
-                HIP_CHECK_M(hipStreamSynchronize(ctx.stream));
+                HIP_CHECK(hipStreamSynchronize(ctx.stream));
                 dg.kernel_launch++;
                 dg.h2d++;
                 dg.d2h++;

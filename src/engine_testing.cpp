@@ -1,0 +1,386 @@
+// Test-only entry points of the GPU engines (declared in engine_gpu.hpp): host
+// validation, single devpool iterations and iteration chains built from the
+// engines' own buffer set, problem descriptors and launch policy
+// (engine_internal.hpp), and the eval-only kernels. No search runs through
+// this file.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <stdexcept>
+#include <string>
+#include <vector>
+
+#include "engine_gpu.hpp"
+#include "engine_internal.hpp"
+#include "gpu_api.hpp"
+#include "search_host.hpp"
+#include "taillard.hpp"
+
+namespace gats {
+
+// ---------------------------------------------------------------------------
+// Single-iteration entry points: upload a chosen pool, run exactly ONE
+// devpool iteration through the problem descriptor's enqueue(), read the
+// pool and the next control block back. The step tests compare every byte
+// and counter with a CPU oracle.
+// ---------------------------------------------------------------------------
+
+namespace {
+
+int presum_mode(const std::string& presum) {
+  if (presum == "auto") return -1;
+  if (presum == "on") return 1;
+  if (presum == "off") return 0;
+  throw std::invalid_argument("presum must be 'auto', 'on' or 'off'");
+}
+
+void validate_step_window(size_t n, int per, unsigned long long m, unsigned long long M,
+                          unsigned long long capacity) {
+  if (m < 1) throw std::invalid_argument("m must be >= 1");
+  if (M < 1) throw std::invalid_argument("M must be >= 1");
+  if (M > (1ull << 31) / static_cast<unsigned long long>(per))
+    throw std::invalid_argument("M * branching must be <= 2^31");
+  if (capacity < n) throw std::invalid_argument("capacity must be >= the number of nodes");
+}
+
+template <class NodeT>
+DevpoolStepCtl step_readback(std::vector<NodeT>& nodes, const NodeT* pool_d,
+                             const DevCtl* ctl_next_d, unsigned long long capacity,
+                             hipStream_t s) {
+  DevCtl fin{};
+  HIP_CHECK(hipMemcpyAsync(&fin, ctl_next_d, sizeof(DevCtl), hipMemcpyDeviceToHost, s));
+  HIP_CHECK(hipStreamSynchronize(s));
+  if (fin.size > capacity) throw std::runtime_error("devpool step: size exceeds capacity");
+  nodes.resize(fin.size);
+  if (fin.size > 0) {
+    HIP_CHECK(hipMemcpyAsync(nodes.data(), pool_d, fin.size * sizeof(NodeT),
+                             hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+  }
+  return {fin.size, fin.chunk, fin.tree, fin.sol, fin.iters, fin.best, fin.overflow};
+}
+
+}  // namespace
+
+void validate_nq_step(const std::vector<NQNode>& nodes, int N, int g, int finish,
+                      unsigned long long m, unsigned long long M,
+                      unsigned long long capacity, const std::string& presum) {
+  // the expand kernel stages EMIT_TILE / 4 + 2 parents per block: N >= 4
+  if (N < 4 || N > MAX_JOBS) throw std::invalid_argument("N must be in 4..20");
+  if (g < 1) throw std::invalid_argument("g must be >= 1");
+  if (finish < -1 || finish > 8) throw std::invalid_argument("finish must be in -1..8");
+  validate_step_window(nodes.size(), N, m, M, capacity);
+  presum_mode(presum);
+  for (size_t i = 0; i < nodes.size(); i++) {
+    const NQNode& p = nodes[i];
+    if (p.depth > N)
+      throw std::invalid_argument("node " + std::to_string(i) + ": depth > N");
+    uint32_t seen = 0;
+    for (int j = 0; j < N; j++) {
+      if (p.board[j] >= N || (seen >> p.board[j] & 1u))
+        throw std::invalid_argument("node " + std::to_string(i) +
+                                    ": board[0:N] is not a permutation of 0..N-1");
+      seen |= 1u << p.board[j];
+    }
+  }
+}
+
+void validate_pfsp_step(const std::vector<PFSPNode>& nodes, int inst, const std::string& lb,
+                        unsigned long long m, unsigned long long M,
+                        unsigned long long capacity, int geom, const std::string& presum,
+                        const std::string& br_str) {
+  const LbKind lbk = lb_from_string(lb);
+  const Branching br = branching_from_string(br_str);
+  check_branching_supported(lbk, br, true);
+  const int jobs = taillard_nb_jobs(inst);
+  if (jobs > MAX_JOBS)
+    throw std::invalid_argument("instance exceeds MAX_JOBS=20 (use ta001..ta030)");
+  if (geom != -1 && geom != 2 && geom != 3)
+    throw std::invalid_argument("geom must be -1, 2 or 3");
+  if (geom != -1 && lbk != LbKind::LB2)
+    throw std::invalid_argument("geom 2/3 select an lb2 kernel: lb must be 'lb2'");
+  validate_step_window(nodes.size(), jobs, m, M, capacity);
+  presum_mode(presum);
+  for (size_t i = 0; i < nodes.size(); i++) {
+    const PFSPNode& p = nodes[i];
+    if (p.depth < 0 || p.depth > jobs - 1)
+      throw std::invalid_argument("node " + std::to_string(i) + ": depth not in 0..jobs-1");
+    if (br == Branching::FWD) {
+      // the forward kernels take limit2 == jobs for granted
+      if (p.limit1 != p.depth - 1)
+        throw std::invalid_argument("node " + std::to_string(i) + ": limit1 != depth - 1");
+      if (p.nback != 0)
+        throw std::invalid_argument("node " + std::to_string(i) +
+                                    ": nback != 0 needs a non-fwd branching rule");
+    } else if (p.limit1 < -1 || p.limit1 + 1 + static_cast<int>(p.nback) != p.depth) {
+      throw std::invalid_argument("node " + std::to_string(i) +
+                                  ": depth != limit1 + 1 + nback");
+    }
+    uint32_t seen = 0;
+    for (int j = 0; j < jobs; j++) {
+      if (p.prmu[j] >= jobs || (seen >> p.prmu[j] & 1u))
+        throw std::invalid_argument("node " + std::to_string(i) +
+                                    ": prmu[0:jobs] is not a permutation of 0..jobs-1");
+      seen |= 1u << p.prmu[j];
+    }
+  }
+}
+
+namespace {
+
+// The geometry a PFSP step / chain call runs: devpool_lbk_geom's choice
+// unless the caller forces an lb2 kernel.
+PfspDevProblem pfsp_step_problem(const PfspInstance& I, const std::string& lb, int geom) {
+  return {I, geom < 0 ? devpool_lbk_geom(lbk_of(lb_from_string(lb)), I.machines) : geom};
+}
+
+// Callers validate first: nothing here runs before their checks passed.
+template <class Problem>
+DevpoolStepCtl devpool_step(const Problem& problem, std::vector<typename Problem::Node>& nodes,
+                            int best, unsigned long long m, unsigned long long M,
+                            unsigned long long capacity, int pm, int device) {
+  using NodeT = typename Problem::Node;
+  const size_t n = nodes.size();
+  // grids sized to the pool that exists, like the engine loops' chunk bound
+  // (bound >= size, so min(size, Mi) == min(size, M))
+  const unsigned long long Mi = std::min<unsigned long long>(M, std::max<size_t>(n, 1));
+  set_device_cached(device);
+  const Problem P = problem.on_device(device);
+  StreamGuard stream;
+  const DevpoolBufs<NodeT> bufs(capacity, Mi, P.per, P.lbg, Problem::needs_be,
+                                /*group_sums=*/true);
+  // auto: the slice thread's sizing rule (the frontier builder's is its
+  // lbg == 2 half)
+  const bool ps = pm < 0 ? devpool_presum_alloc(bufs.G, P.lbg) : pm == 1;
+  DevCtl ctl{};
+  ctl.size = n;
+  ctl.best = best;
+  if (n > 0)
+    HIP_CHECK(hipMemcpyAsync(bufs.pool.p, nodes.data(), n * sizeof(NodeT),
+                             hipMemcpyHostToDevice, stream.s));
+  upload_ctl_pair(bufs.ctl.p, ctl, stream.s);
+  P.enqueue(bufs, bufs.ctl.p, bufs.ctl.p + 1, m, Mi, ps, stream.s);
+  HIP_CHECK(hipGetLastError());
+  return step_readback(nodes, bufs.pool.p, bufs.ctl.p + 1, capacity, stream.s);
+}
+
+}  // namespace
+
+DevpoolStepCtl nq_devpool_step(std::vector<NQNode>& nodes, int N, int g, int finish,
+                               unsigned long long m, unsigned long long M,
+                               unsigned long long capacity, const std::string& presum,
+                               int device) {
+  validate_nq_step(nodes, N, g, finish, m, M, capacity, presum);  // before any HIP call
+  return devpool_step(NqDevProblem(N, g, finish), nodes, /*best=*/0, m, M, capacity,
+                      presum_mode(presum), device);
+}
+
+DevpoolStepCtl pfsp_devpool_step(std::vector<PFSPNode>& nodes, int inst, const std::string& lb,
+                                 int best, unsigned long long m, unsigned long long M,
+                                 unsigned long long capacity, int geom,
+                                 const std::string& presum, int device,
+                                 const std::string& br) {
+  validate_pfsp_step(nodes, inst, lb, m, M, capacity, geom, presum, br);  // before any HIP call
+  const PfspInstance& I = pfsp_instance_cached(inst, 1, branching_from_string(br));
+  return devpool_step(pfsp_step_problem(I, lb, geom), nodes, best, m, M, capacity,
+                      presum_mode(presum), device);
+}
+
+// ---------------------------------------------------------------------------
+// Chain entry points (declared in engine_gpu.hpp): k iterations back to back
+// over ONE set of buffers sized for the largest window, alternating control
+// blocks, no host synchronisation in between — the launch shape of the engine
+// threads, minus the loop driver. A snapshot of the live control block and of
+// the pool follows every iteration on the same stream.
+// ---------------------------------------------------------------------------
+
+namespace {
+
+constexpr unsigned long long CHAIN_MAX_ITERS = 16;
+constexpr unsigned long long CHAIN_MAX_NODES = 1ull << 22;  // capacity * (k + 1)
+
+void validate_chain_windows(const std::vector<unsigned long long>& windows, int per,
+                            unsigned long long capacity) {
+  const unsigned long long k = windows.size();
+  if (k < 1 || k > CHAIN_MAX_ITERS)
+    throw std::invalid_argument("windows must hold 1..16 entries");
+  for (unsigned long long w : windows) {
+    if (w < 1) throw std::invalid_argument("every window must be >= 1");
+    if (w > (1ull << 31) / static_cast<unsigned long long>(per))
+      throw std::invalid_argument("window * branching must be <= 2^31");
+  }
+  if (capacity > CHAIN_MAX_NODES / (k + 1))
+    throw std::invalid_argument("capacity * (len(windows) + 1) must be <= 2^22 nodes");
+}
+
+// Callers validate first: nothing here runs before their checks passed.
+template <class Problem>
+std::vector<DevpoolSnapshot<typename Problem::Node>> devpool_chain(
+    const Problem& problem, const std::vector<typename Problem::Node>& nodes, int best,
+    unsigned long long m, const std::vector<unsigned long long>& windows,
+    unsigned long long capacity, int pm, int device) {
+  using NodeT = typename Problem::Node;
+  const unsigned long long Mc = *std::max_element(windows.begin(), windows.end());
+  set_device_cached(device);
+  const Problem P = problem.on_device(device);
+  StreamGuard stream;
+  const hipStream_t s = stream.s;
+  // sized ONCE for the largest window, as a slice thread sizes them for Mc
+  const bool presum_alloc = devpool_presum_alloc(devpool_grid(Mc, P.per, P.lbg), P.lbg);
+  const DevpoolBufs<NodeT> bufs(capacity, Mc, P.per, P.lbg, Problem::needs_be,
+                                presum_alloc || pm == 1);
+  NodeT* const pool_d = bufs.pool.p;
+  DevCtl* const ctl_d = bufs.ctl.p;
+  const size_t n = nodes.size();
+  const size_t k = windows.size();
+  DevGuard<NodeT> snap_pool_d(std::max<size_t>(capacity * k, 1));
+  DevGuard<DevCtl> snap_ctl_d(k);
+  DevCtl ctl{};
+  ctl.size = n;
+  ctl.best = best;
+  if (n > 0)
+    HIP_CHECK(hipMemcpyAsync(pool_d, nodes.data(), n * sizeof(NodeT), hipMemcpyHostToDevice, s));
+  upload_ctl_pair(ctl_d, ctl, s);
+  for (size_t i = 0; i < k; i++) {
+    DevCtl* cur = ctl_d + (i & 1);
+    DevCtl* next = ctl_d + 1 - (i & 1);
+    const DevIterPolicy it = devpool_iter_policy(Mc, windows[i], P.per, P.lbg, presum_alloc);
+    P.enqueue(bufs, cur, next, m, it.Mi, pm < 0 ? it.ps : pm == 1, s);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipMemcpyAsync(snap_ctl_d.p + i, next, sizeof(DevCtl), hipMemcpyDeviceToDevice, s));
+    if (capacity > 0)
+      HIP_CHECK(hipMemcpyAsync(snap_pool_d.p + i * capacity, pool_d, capacity * sizeof(NodeT),
+                               hipMemcpyDeviceToDevice, s));
+  }
+  std::vector<DevCtl> fin(k);
+  HIP_CHECK(hipMemcpyAsync(fin.data(), snap_ctl_d.p, k * sizeof(DevCtl), hipMemcpyDeviceToHost, s));
+  HIP_CHECK(hipStreamSynchronize(s));
+
+  std::vector<DevpoolSnapshot<NodeT>> out(k);
+  // live size entering iteration i, and the un-popped prefix once overflowed:
+  // the overflowing iteration leaves [base, ..) undefined and every later
+  // iteration pops nothing, so that prefix is what all later snapshots keep
+  unsigned long long prev = n, ovf_base = 0;
+  bool overflowed = false;
+  for (size_t i = 0; i < k; i++) {
+    const DevCtl& f = fin[i];
+    unsigned long long keep;
+    if (f.overflow) {
+      if (!overflowed) {
+        const unsigned long long c = prev < m ? 0 : std::min(prev, windows[i]);
+        ovf_base = prev - c;
+        overflowed = true;
+      }
+      keep = ovf_base;
+    } else {
+      if (f.size > capacity) throw std::runtime_error("devpool chain: size exceeds capacity");
+      keep = f.size;
+      prev = f.size;
+    }
+    if (keep > capacity) throw std::runtime_error("devpool chain: prefix exceeds capacity");
+    out[i].nodes.resize(keep);
+    if (keep > 0)
+      HIP_CHECK(hipMemcpyAsync(out[i].nodes.data(), snap_pool_d.p + i * capacity,
+                               keep * sizeof(NodeT), hipMemcpyDeviceToHost, s));
+    out[i].ctl = {f.size, f.chunk, f.tree, f.sol, f.iters, f.best, f.overflow};
+  }
+  HIP_CHECK(hipStreamSynchronize(s));
+  return out;
+}
+
+}  // namespace
+
+std::vector<DevpoolSnapshot<NQNode>> nq_devpool_chain(
+    const std::vector<NQNode>& nodes, int N, int g, int finish, unsigned long long m,
+    const std::vector<unsigned long long>& windows, unsigned long long capacity,
+    const std::string& presum, int device) {
+  validate_nq_step(nodes, N, g, finish, m, 1, capacity, presum);  // before any HIP call
+  validate_chain_windows(windows, N, capacity);
+  return devpool_chain(NqDevProblem(N, g, finish), nodes, /*best=*/0, m, windows, capacity,
+                       presum_mode(presum), device);
+}
+
+std::vector<DevpoolSnapshot<PFSPNode>> pfsp_devpool_chain(
+    const std::vector<PFSPNode>& nodes, int inst, const std::string& lb, int best,
+    unsigned long long m, const std::vector<unsigned long long>& windows,
+    unsigned long long capacity, int geom, const std::string& presum, int device,
+    const std::string& br) {
+  validate_pfsp_step(nodes, inst, lb, m, 1, capacity, geom, presum, br);  // before any HIP call
+  validate_chain_windows(windows, taillard_nb_jobs(inst), capacity);
+  const PfspInstance& I = pfsp_instance_cached(inst, 1, branching_from_string(br));
+  return devpool_chain(pfsp_step_problem(I, lb, geom), nodes, best, m, windows, capacity,
+                       presum_mode(presum), device);
+}
+
+// ---------------------------------------------------------------------------
+// Eval-only entry points (HIP-kernel-vs-CPU-oracle numerics tests)
+// ---------------------------------------------------------------------------
+
+std::vector<uint8_t> nq_gpu_labels(int N, int g, const std::vector<NQNode>& nodes,
+                                   int device) {
+  set_device_cached(device);
+  const size_t n = nodes.size();
+  std::vector<uint8_t> labels(n * N, 255);
+  DevGuard<NQNode> parents_d(n);
+  DevGuard<uint8_t> labels_d(n * N);
+  HIP_CHECK(hipMemcpy(parents_d.p, nodes.data(), n * sizeof(NQNode), hipMemcpyHostToDevice));
+  HIP_CHECK(hipMemset(labels_d.p, 255, n * N));
+  launch_nq_eval(parents_d.p, static_cast<int>(n), N, g, labels_d.p, nullptr);
+  HIP_CHECK(hipMemcpy(labels.data(), labels_d.p, n * N, hipMemcpyDeviceToHost));
+  return labels;
+}
+
+std::vector<int32_t> pfsp_gpu_bounds(int inst, const std::string& lb_str,
+                                     const std::vector<PFSPNode>& nodes, int best,
+                                     int device) {
+  const LbKind lb = lb_from_string(lb_str);
+  PfspInstance I = make_pfsp_instance(inst, 1);
+  set_device_cached(device);
+  PfspTablesGuard tables(I);
+  const size_t n = nodes.size();
+  std::vector<int32_t> bounds(n * I.jobs, -1);
+  DevGuard<PFSPNode> parents_d(n);
+  DevGuard<int32_t> bounds_d(n * I.jobs);
+  HIP_CHECK(hipMemcpy(parents_d.p, nodes.data(), n * sizeof(PFSPNode), hipMemcpyHostToDevice));
+  HIP_CHECK(hipMemset(bounds_d.p, 255, n * I.jobs * sizeof(int32_t)));
+  launch_pfsp_eval(parents_d.p, static_cast<int>(n), I.jobs, I.machines, lbk_of(lb),
+                   tables.tb, best, bounds_d.p, nullptr);
+  HIP_CHECK(hipMemcpy(bounds.data(), bounds_d.p, n * I.jobs * sizeof(int32_t),
+                      hipMemcpyDeviceToHost));
+  return bounds;
+}
+
+std::pair<std::vector<int32_t>, std::vector<int32_t>> pfsp_gpu_bounds_bi(
+    int inst, const std::vector<PFSPNode>& nodes, int device) {
+  PfspInstance I = make_pfsp_instance(inst, 1);
+  // the kernel indexes prmu by [limit1 + 1, jobs - nback): check before any HIP call
+  for (size_t i = 0; i < nodes.size(); i++) {
+    const PFSPNode& p = nodes[i];
+    if (p.limit1 < -1 || p.limit1 + 1 + static_cast<int>(p.nback) > I.jobs)
+      throw std::invalid_argument("node " + std::to_string(i) +
+                                  ": limit1 + 1 + nback exceeds jobs");
+    for (int j = 0; j < I.jobs; j++)
+      if (p.prmu[j] >= I.jobs)
+        throw std::invalid_argument("node " + std::to_string(i) + ": prmu entry >= jobs");
+  }
+  set_device_cached(device);
+  PfspTablesGuard tables(I);
+  const size_t n = nodes.size();
+  std::vector<int32_t> lb_begin(n * I.jobs, -1), lb_end(n * I.jobs, -1);
+  if (n == 0) return {lb_begin, lb_end};
+  DevGuard<PFSPNode> parents_d(n);
+  DevGuard<int32_t> begin_d(n * I.jobs), end_d(n * I.jobs);
+  HIP_CHECK(hipMemcpy(parents_d.p, nodes.data(), n * sizeof(PFSPNode), hipMemcpyHostToDevice));
+  HIP_CHECK(hipMemset(begin_d.p, 255, n * I.jobs * sizeof(int32_t)));
+  HIP_CHECK(hipMemset(end_d.p, 255, n * I.jobs * sizeof(int32_t)));
+  (void)hipGetLastError();  // drop a stale launch error of an earlier, unchecked call
+  launch_pfsp_eval(parents_d.p, static_cast<int>(n), I.jobs, I.machines, 0, tables.tb, 0,
+                   begin_d.p, nullptr, static_cast<int>(Branching::MINBRANCH), end_d.p);
+  HIP_CHECK(hipGetLastError());
+  HIP_CHECK(hipMemcpy(lb_begin.data(), begin_d.p, n * I.jobs * sizeof(int32_t),
+                      hipMemcpyDeviceToHost));
+  HIP_CHECK(hipMemcpy(lb_end.data(), end_d.p, n * I.jobs * sizeof(int32_t),
+                      hipMemcpyDeviceToHost));
+  return {lb_begin, lb_end};
+}
+}  // namespace gats

@@ -4,7 +4,7 @@ test_gpu_devpool_step.py pins expand -> presum -> gather2 for one iteration
 whose grid is clamped to the pool and whose buffers are fresh. The engine
 threads differ in four ways, all covered here through nq_devpool_chain /
 pfsp_devpool_chain (k eager iterations on one stream through
-enqueue_*_iter, no host synchronisation in between, a snapshot of the control
+the problem descriptor's enqueue(), no host synchronisation in between, a snapshot of the control
 block and the pool after each):
 
   * grids far wider than the chunk (most expand blocks start past its end,
