@@ -65,7 +65,7 @@ def _stats_line(path, args, r):
     tier_tag = {"seq": "SEQ", "gpu": "S-GPU", "multigpu": "M-GPU", "dist": "D-GPU"}[args.tier]
     with open(path, "a") as f:
         if args.problem == "pfsp":
-            lb_num = {"lb1": 1, "lb1_d": 0, "lb2": 2}[args.lb]
+            lb_num = {"lb1": 1, "lb1_d": 0, "lb2": 2, "lb12": 12}[args.lb]
             f.write(f"ta{args.inst} lb{lb_num} {tier_tag} {r['time']:.4f} "
                     f"{r['tree']} {r['sol']} {r['optimum']}\n")
         else:
@@ -113,13 +113,17 @@ def main(argv=None):
 
     pf = sub.add_parser("pfsp", help="PFSP Branch-and-Bound (Taillard instances)")
     pf.add_argument("--inst", type=int, default=14, help="Taillard instance (1..120)")
-    pf.add_argument("--lb", default="lb1", choices=["lb1", "lb1_d", "lb2"])
+    pf.add_argument("--lb", default="lb1", choices=["lb1", "lb1_d", "lb2", "lb12"],
+                    help="lower bound: lb1, lb1_d (incremental lb1), lb2 (Johnson), lb12 "
+                         "(lb1_d picks the direction and filters the children, lb2 bounds "
+                         "the survivors; tiers seq and gpu, every --br)")
     pf.add_argument("--ub", type=int, default=1, choices=[0, 1],
                     help="initial upper bound: 1=known optimum, 0=inf")
     pf.add_argument("--br", default="fwd", choices=["fwd", "bwd", "alt", "minbranch"],
                     help="branching rule: fwd (reference), bwd, alt (by depth parity), "
                          "minbranch (per node, the side with fewer surviving children; "
-                         "lb1_d only). Non-fwd rules: tiers seq and gpu (gpu: lb1_d)")
+                         "lb1_d or lb12). Non-fwd rules: tiers seq and gpu (gpu: lb1_d "
+                         "or lb12)")
     add_common(pf)
 
     args = ap.parse_args(argv)
@@ -162,10 +166,14 @@ def main(argv=None):
         if args.br != "fwd" and args.tier in ("multigpu", "dist"):
             ap.error(f"--br {args.br} is not yet supported on tier {args.tier} "
                      "(fwd only; use --tier seq or --tier gpu)")
-        if args.br == "minbranch" and args.lb != "lb1_d":
-            ap.error("--br minbranch needs --lb lb1_d")
-        if args.br != "fwd" and args.tier == "gpu" and args.lb != "lb1_d":
-            ap.error(f"--br {args.br} on tier gpu needs --lb lb1_d")
+        if args.lb == "lb12" and args.tier in ("multigpu", "dist"):
+            ap.error(f"--lb lb12 is not yet supported on tier {args.tier} "
+                     "(use --tier seq or --tier gpu)")
+        if args.lb != "lb12":
+            if args.br == "minbranch" and args.lb != "lb1_d":
+                ap.error("--br minbranch needs --lb lb1_d")
+            if args.br != "fwd" and args.tier == "gpu" and args.lb != "lb1_d":
+                ap.error(f"--br {args.br} on tier gpu needs --lb lb1_d")
         jobs, machines = c.taillard_nb_jobs(inst), c.taillard_nb_machines(inst)
         init_ub = c.taillard_best_ub(inst) if args.ub == 1 else float("inf")
         tier_name = {"seq": "Sequential", "gpu": "Single-GPU", "multigpu": "Multi-GPU",

@@ -214,8 +214,15 @@ def run_nqueens(N, g=1, m=25, M=50000, mode="devpool", capacity=1 << 27,
     return _reduce_stats(r, phase1, local_dev, world)
 
 
+def _reject_lb12(lb):
+    # before init_dist and any HIP call
+    if lb == "lb12":
+        raise ValueError("bound 'lb12' is not yet supported on the dist tier")
+
+
 def run_pfsp(inst, lb="lb1", ub=1, m=25, M=50000, mode="devpool", capacity=1 << 24,
              frontier_target=None, engine="gpu"):
+    _reject_lb12(lb)
     c = gats_amd.core()
     rank, world = init_dist()
     if (world == 1 and engine == "gpu" and mode == "devpool"
@@ -275,6 +282,7 @@ def run_pfsp_shared_ub(inst, lb="lb1", ub=1, m=25, M=50000, capacity=1 << 24,
     incumbent >= optimum is a valid UB)."""
     import time
 
+    _reject_lb12(lb)
     c = gats_amd.core()
     rank, world = init_dist()
     if frontier_target is None:
@@ -444,6 +452,7 @@ def run_pfsp_live(inst, lb="lb1", ub=1, m=25, M=50000, capacity=1 << 24,
     boundary), so counts stay exact at ub=1."""
     import time
 
+    _reject_lb12(lb)
     c = gats_amd.core()
     rank, world = init_dist()
     if frontier_target is None:
@@ -558,6 +567,7 @@ def run_from_cli(args):
     the tier with the CPU evaluator (CI coverage of the full CLI dist path
     without a GPU; the ub=0 mid-search UB exchange needs the GPU engine and
     falls back to the end-of-search min-reduce)."""
+    _reject_lb12(getattr(args, "lb", None))
     if getattr(args, "br", "fwd") != "fwd":
         raise ValueError(f"branching rule '{args.br}' is not yet supported on the dist tier "
                          "(fwd only)")

@@ -134,6 +134,20 @@ py::tuple pfsp_cpu_bounds_bi(int inst, const py::bytes& pool_bytes) {
   return py::make_tuple(lb_begin, lb_end);
 }
 
+// lb12 twin of pfsp_gpu_bounds_lb12: (dir bytes, bounds) from the host rule.
+py::tuple pfsp_cpu_bounds_lb12(int inst, const py::bytes& pool_bytes, int best,
+                               const std::string& br_str) {
+  PfspInstance I = make_pfsp_instance(inst, 1, branching_from_string(br_str));
+  auto nodes = nodes_from_bytes<PFSPNode>(pool_bytes);
+  validate_lb12_nodes(nodes, I.jobs);
+  std::vector<uint8_t> dir(nodes.size(), 255);
+  std::vector<int32_t> bounds(nodes.size() * I.jobs, -1);
+  for (size_t i = 0; i < nodes.size(); i++)
+    pfsp_lb12_eval(I, nodes[i], best, dir[i], bounds.data() + i * I.jobs);
+  return py::make_tuple(py::bytes(reinterpret_cast<const char*>(dir.data()), dir.size()),
+                        bounds);
+}
+
 py::tuple nq_bfs_frontier(int N, int g, size_t target) {
   Pool<NQNode> pool;
   pool.pushBack(nq_root());
@@ -164,7 +178,8 @@ py::tuple pfsp_gpu_frontier_py(int inst, const std::string& lb_str, int ub, size
   const Branching br = branching_from_string(br_str);
   check_branching_supported(lb, br, true);
   PfspInstance I = make_pfsp_instance(inst, ub, br);
-  const int lbk = (lb == LbKind::LB1_D) ? 0 : (lb == LbKind::LB1 ? 1 : 2);
+  const int lbk =
+      (lb == LbKind::LB1_D) ? 0 : (lb == LbKind::LB1 ? 1 : (lb == LbKind::LB12 ? 4 : 2));
   uint64_t tree = 0, sol = 0;
   int best = I.init_ub;
   std::vector<PFSPNode> nodes;
@@ -568,6 +583,18 @@ PYBIND11_MODULE(_core, mod) {
             return py::make_tuple(r.first, r.second);
           },
           py::arg("inst"), py::arg("nodes"), py::arg("device") = 0);
+  mod.def("pfsp_cpu_bounds_lb12", &pfsp_cpu_bounds_lb12, py::arg("inst"), py::arg("nodes"),
+          py::arg("best"), py::arg("br"));
+  mod.def("pfsp_gpu_bounds_lb12",
+          [](int inst, const py::bytes& nodes, int best, const std::string& br, int device) {
+            auto v = nodes_from_bytes<PFSPNode>(nodes);
+            auto r = pfsp_gpu_bounds_lb12(inst, v, best, br, device);
+            return py::make_tuple(
+                py::bytes(reinterpret_cast<const char*>(r.first.data()), r.first.size()),
+                r.second);
+          },
+          py::arg("inst"), py::arg("nodes"), py::arg("best"), py::arg("br"),
+          py::arg("device") = 0);
   mod.def("nq_gpu_labels",
           [](int N, int g, const py::bytes& nodes, int device) {
             auto v = nodes_from_bytes<NQNode>(nodes);

@@ -553,7 +553,9 @@ static DevCtl run_devpool_loop(hipStream_t s, DevCtl* ctl_d, const DevLoopCfg& c
 // hide kernel-boundary bubbles (measured N=17: S=1 89.3 ms, S=2 77.4,
 // S=4 79.6, S=6 84.2). lb2 keeps the narrow --M chunk (per-wave grid), so
 // its kernels are short and need 4 chains (ta005 20x5: S=2 41.4 s,
-// S=4 31.5 s; ta021 20x20 is S-insensitive).
+// S=4 31.5 s; ta021 20x20 is S-insensitive). lb12 (code 4) starts from the
+// lb1_d choices here and in devpool_chunk_cap: its grid is per parent like
+// lb1_d's, but neither choice has been measured for its kernel yet.
 static int devpool_slices(int lbk = 1) {
   if (const char* e = std::getenv("GATS_SLICES")) {
     int v = atoi(e);
@@ -986,9 +988,9 @@ DevpoolMultiOut nq_devpool_multi(Pool<NQNode>& pool, int N, int g, int m, int M,
 }
 
 static void check_devpool_branching(const PfspInstance& I, int lbk) {
-  if (I.br != Branching::FWD && lbk != 0)
+  if (I.br != Branching::FWD && lbk != 0 && lbk != 4)
     throw std::invalid_argument(std::string("branching rule '") + branching_name(I.br) +
-                                "' on the gpu tier needs lb1_d");
+                                "' on the gpu tier needs lb1_d or lb12");
 }
 
 DevpoolMultiOut pfsp_devpool_multi(const PfspInstance& I, Pool<PFSPNode>& pool, int lbk,
@@ -1151,7 +1153,16 @@ Result pfsp_gpu_run(const PfspInstance& I, LbKind lb, Pool<PFSPNode>& pool, int 
     DevGuard<int32_t> bounds_d(static_cast<size_t>(M) * jobs);
     // non-fwd branching rules: the kernel returns both directions' bounds
     // (lb_begin in bounds, lb_end in bounds2) and the host picks per parent
-    const bool bi = I.br != Branching::FWD;
+    // lb12: the kernel picks the direction and filters with this batch's
+    // incumbent; the host applies dir / bounds with its live one
+    const bool l12 = lb == LbKind::LB12;
+    std::unique_ptr<PinnedGuard<uint8_t>> dirs;
+    std::unique_ptr<DevGuard<uint8_t>> dirs_d;
+    if (l12) {
+      dirs.reset(new PinnedGuard<uint8_t>(M));
+      dirs_d.reset(new DevGuard<uint8_t>(M));
+    }
+    const bool bi = !l12 && I.br != Branching::FWD;
     if (bi) check_branching_supported(lb, I.br, true);
     std::unique_ptr<PinnedGuard<int32_t>> bounds2;
     std::unique_ptr<DevGuard<int32_t>> bounds2_d;
@@ -1166,7 +1177,9 @@ Result pfsp_gpu_run(const PfspInstance& I, LbKind lb, Pool<PFSPNode>& pool, int 
                                hipMemcpyHostToDevice, stream.s));
       launch_pfsp_eval(parents_d.p, static_cast<int>(n), jobs, machines, lbk, tb_dev, best,
                        bounds_d.p, stream.s, static_cast<int>(I.br),
-                       bi ? bounds2_d->p : nullptr);
+                       bi ? bounds2_d->p : nullptr, l12 ? dirs_d->p : nullptr);
+      if (l12)
+        HIP_CHECK(hipMemcpyAsync(dirs->p, dirs_d->p, n, hipMemcpyDeviceToHost, stream.s));
       HIP_CHECK(hipMemcpyAsync(bounds.p, bounds_d.p, n * jobs * sizeof(int32_t),
                                hipMemcpyDeviceToHost, stream.s));
       if (bi)
@@ -1175,11 +1188,13 @@ Result pfsp_gpu_run(const PfspInstance& I, LbKind lb, Pool<PFSPNode>& pool, int 
       HIP_CHECK(hipStreamSynchronize(stream.s));
       r.kernel_launch++;
       r.h2d++;
-      r.d2h += bi ? 2 : 1;
+      r.d2h += (bi || l12) ? 2 : 1;
       r.h2d_bytes += n * sizeof(PFSPNode);
-      r.d2h_bytes += (bi ? 2 : 1) * n * jobs * sizeof(int32_t);
+      r.d2h_bytes += (bi ? 2 : 1) * n * jobs * sizeof(int32_t) + (l12 ? n : 0);
       r.gpu_iters++;
-      if (bi)
+      if (l12)
+        pfsp_generate_children_lb12(I, parents.p, n, dirs->p, bounds.p, tree, sol, best, pool);
+      else if (bi)
         pfsp_generate_children_bi(I, parents.p, n, bounds.p, bounds2->p, tree, sol, best,
                                   pool);
       else
@@ -1409,6 +1424,8 @@ PfspAsyncEngine::PfspAsyncEngine(int inst, const std::string& lb_str, int ub, in
                                  const std::string& br)
     : inst_(inst), ub_(ub), m_(m), M_(M), device_(device), lb_(lb_str),
       capacity_(capacity), shared_best_(0) {
+  if (lb_str == "lb12")
+    throw std::invalid_argument("bound 'lb12' is not yet supported by PfspAsyncEngine");
   if (branching_from_string(br) != Branching::FWD)
     throw std::invalid_argument("branching rule '" + br +
                                 "' is not yet supported by PfspAsyncEngine (fwd only)");

@@ -89,8 +89,9 @@ Result nqueens_gpu_from_pool(const std::vector<NQNode>& nodes, int N, int g, int
 
 // br (all PFSP single-GPU entry points): branching rule "fwd" (default, the
 // reference's tree), "bwd", "alt" or "minbranch" (search_host.hpp). Non-fwd
-// rules run the both-directions lb1_d kernels and need lb == "lb1_d"; any
-// other combination throws std::invalid_argument.
+// rules run the both-directions lb1_d kernels and need lb == "lb1_d", or the
+// lb12 kernels (lb == "lb12", every rule); any other combination throws
+// std::invalid_argument.
 Result pfsp_gpu(int inst, const std::string& lb, int ub, int m, int M, int device,
                 const std::string& mode, unsigned long long capacity,
                 const std::string& br = "fwd");
@@ -118,7 +119,7 @@ Result nqueens_multigpu(int N, int g, int m, int M, int D, const std::string& ev
 Result pfsp_multigpu(int inst, const std::string& lb, int ub, int m, int M, int D,
                      const std::string& eval, bool share_best, double perc = 0.5,
                      unsigned long long capacity = 1ull << 27,
-                     const std::string& br = "fwd");  // non-fwd rules: not yet, throws
+                     const std::string& br = "fwd");  // non-fwd rules, lb12: not yet, throws
 
 // Persistent per-rank PFSP engine: a background thread that accepts
 // successive frontiers (submit), runs the devpool search on each, exposes a
@@ -130,7 +131,7 @@ Result pfsp_multigpu(int inst, const std::string& lb, int ub, int m, int M, int 
 // frontier claims pay no re-arm cost.
 class PfspAsyncEngine {
  public:
-  // br: only "fwd" is supported yet; any other rule throws
+  // br: only "fwd" is supported yet; any other rule throws, and so does lb12
   PfspAsyncEngine(int inst, const std::string& lb, int ub, int m, int M, int device,
                   unsigned long long capacity, const std::string& br = "fwd");
   // one-shot convenience (round-1 API): submits `nodes` immediately
@@ -256,5 +257,14 @@ std::vector<int32_t> pfsp_gpu_bounds(int inst, const std::string& lb,
 // front (lb_begin), second = children fixed at the back (lb_end).
 std::pair<std::vector<int32_t>, std::vector<int32_t>> pfsp_gpu_bounds_bi(
     int inst, const std::vector<PFSPNode>& nodes, int device);
+
+// lb12 eval kernel: (dir[n], bounds[n * jobs]) in pfsp_lb12_eval's layout
+// (search_host.hpp; dir 255 / bounds -1 where the kernel writes nothing).
+// Nodes may have jobs fixed at the back under every rule; their structure is
+// checked on the host before any HIP call (validate_lb12_nodes).
+void validate_lb12_nodes(const std::vector<PFSPNode>& nodes, int jobs);
+std::pair<std::vector<uint8_t>, std::vector<int32_t>> pfsp_gpu_bounds_lb12(
+    int inst, const std::vector<PFSPNode>& nodes, int best, const std::string& br,
+    int device);
 
 }  // namespace gats

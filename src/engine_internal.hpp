@@ -92,13 +92,16 @@ const PfspDevTables& pfsp_tables_cached(const PfspInstance& I, int device);
 // sorts) cached per (inst, ub, branching rule).
 const PfspInstance& pfsp_instance_cached(int inst, int ub, Branching br = Branching::FWD);
 
-// Kernel-side bound code: 0 = lb1_d, 1 = lb1, 2 = lb2.
+// Kernel-side bound code: 0 = lb1_d, 1 = lb1, 2 = lb2, 4 = lb12 (3 is the
+// per-lane lb2 GEOMETRY, gpu_api.hpp).
 inline int lbk_of(LbKind lb) {
   switch (lb) {
     case LbKind::LB1_D:
       return 0;
     case LbKind::LB1:
       return 1;
+    case LbKind::LB12:
+      return 4;
     default:
       return 2;
   }
@@ -224,7 +227,8 @@ struct DevIterPolicy {
 // group sums keep gather's prefix walk O(G/256): always needed for lb2's
 // per-wave counts, and for the thread-per-child paths once the chunk is wide
 // (at the wide chunk G is ~8700 blocks and the linear walk dominated gather,
-// 193 us avg at N=17)
+// 193 us avg at N=17). lb12 (code 4) has lb1_d's count granularity and
+// starts from lb1_d's rule; unmeasured for its kernel.
 inline bool devpool_presum_alloc(int G, int lbg) { return lbg == 2 || G > 1024; }
 
 inline DevIterPolicy devpool_iter_policy(unsigned long long Mc, unsigned long long bound,

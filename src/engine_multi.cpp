@@ -422,6 +422,8 @@ Result nqueens_multigpu(int N, int g, int m, int M, int D, const std::string& ev
 Result pfsp_multigpu(int inst, const std::string& lb_str, int ub, int m, int M, int D,
                      const std::string& eval, bool share_best, double perc,
                      unsigned long long capacity, const std::string& br) {
+  if (lb_str == "lb12")
+    throw std::invalid_argument("bound 'lb12' is not yet supported on the multigpu tier");
   if (branching_from_string(br) != Branching::FWD)
     throw std::invalid_argument("branching rule '" + br +
                                 "' is not yet supported on the multigpu tier (fwd only)");

@@ -383,4 +383,48 @@ std::pair<std::vector<int32_t>, std::vector<int32_t>> pfsp_gpu_bounds_bi(
                       hipMemcpyDeviceToHost));
   return {lb_begin, lb_end};
 }
+
+void validate_lb12_nodes(const std::vector<PFSPNode>& nodes, int jobs) {
+  for (size_t i = 0; i < nodes.size(); i++) {
+    const PFSPNode& p = nodes[i];
+    if (p.limit1 < -1 || p.limit1 + 1 + static_cast<int>(p.nback) > jobs)
+      throw std::invalid_argument("node " + std::to_string(i) +
+                                  ": limit1 + 1 + nback exceeds jobs");
+    if (p.depth != p.limit1 + 1 + static_cast<int>(p.nback))
+      throw std::invalid_argument("node " + std::to_string(i) +
+                                  ": depth != limit1 + 1 + nback");
+    for (int j = 0; j < jobs; j++)
+      if (p.prmu[j] >= jobs)
+        throw std::invalid_argument("node " + std::to_string(i) + ": prmu entry >= jobs");
+  }
+}
+
+std::pair<std::vector<uint8_t>, std::vector<int32_t>> pfsp_gpu_bounds_lb12(
+    int inst, const std::vector<PFSPNode>& nodes, int best, const std::string& br_str,
+    int device) {
+  const Branching br = branching_from_string(br_str);
+  PfspInstance I = make_pfsp_instance(inst, 1, br);
+  validate_lb12_nodes(nodes, I.jobs);  // before any HIP call
+  const size_t n = nodes.size();
+  std::vector<uint8_t> dir(n, 255);
+  std::vector<int32_t> bounds(n * I.jobs, -1);
+  if (n == 0) return {dir, bounds};
+  set_device_cached(device);
+  PfspTablesGuard tables(I);
+  DevGuard<PFSPNode> parents_d(n);
+  DevGuard<uint8_t> dir_d(n);
+  DevGuard<int32_t> bounds_d(n * I.jobs);
+  HIP_CHECK(hipMemcpy(parents_d.p, nodes.data(), n * sizeof(PFSPNode), hipMemcpyHostToDevice));
+  HIP_CHECK(hipMemset(dir_d.p, 255, n));
+  HIP_CHECK(hipMemset(bounds_d.p, 255, n * I.jobs * sizeof(int32_t)));
+  (void)hipGetLastError();  // drop a stale launch error of an earlier, unchecked call
+  launch_pfsp_eval(parents_d.p, static_cast<int>(n), I.jobs, I.machines, lbk_of(LbKind::LB12),
+                   tables.tb, best, bounds_d.p, nullptr, static_cast<int>(br), nullptr,
+                   dir_d.p);
+  HIP_CHECK(hipGetLastError());
+  HIP_CHECK(hipMemcpy(dir.data(), dir_d.p, n, hipMemcpyDeviceToHost));
+  HIP_CHECK(hipMemcpy(bounds.data(), bounds_d.p, n * I.jobs * sizeof(int32_t),
+                      hipMemcpyDeviceToHost));
+  return {dir, bounds};
+}
 }  // namespace gats

@@ -62,18 +62,22 @@ struct PfspDevTables {
 // hostpool eval (labels/bounds out):
 void launch_nq_eval(const NQNode* parents, int n, int N, int g, uint8_t* labels,
                     hipStream_t s);
-// lbk: 0 = lb1_d, 1 = lb1, 2 = lb2
+// lbk: 0 = lb1_d, 1 = lb1, 2 = lb2, 4 = lb12
 // br: branching rule code (0 fwd, 1 bwd, 2 alt, 3 minbranch = the Branching
 // enum). br == 0 launches the forward kernels; br != 0 requires lbk == 0 and
 // launches the both-directions lb1_d kernel, which fills `bounds` (front
 // children) and `bounds_end` (back children), both [n * jobs] by position.
+// lbk == 4 takes every br and fills dir[n] (0 front, 1 back) and `bounds`
+// (pfsp_lb12_eval's layout; positions outside a parent's unscheduled range
+// are left untouched).
 void launch_pfsp_eval(const PFSPNode* parents, int n, int jobs, int machines, int lbk,
                       const PfspDevTables& tb, int best, int32_t* bounds, hipStream_t s,
-                      int br = 0, int32_t* bounds_end = nullptr);
+                      int br = 0, int32_t* bounds_end = nullptr, uint8_t* dir = nullptr);
 
 // devpool v3 (see kernels.hip): expand -> scan -> gather, 3 kernels/iteration.
 // lbk geometry codes: 0 lb1_d, 1 thread-per-child, 2 wave-coop lb2,
-// 3 per-lane lb2 with thread-per-child geometry (machines <= 10).
+// 3 per-lane lb2 with thread-per-child geometry (machines <= 10),
+// 4 lb12 (the lb1_d geometry; k_pfsp_x_lb12 takes every branching rule).
 int devpool_lbk_geom(int lbk, int machines);
 int devpool_grid(unsigned long long M, int per, int lbk);
 int devpool_stride(int lbk);

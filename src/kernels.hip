@@ -1090,6 +1090,65 @@ __device__ inline int wave_max_i32(int v) {
   return v;
 }
 
+// One child's Johnson sweep spread over a wave: lane l bounds the
+// strength-ordered pairs l, l + 64, ... and after each 64-pair round a shfl
+// max-reduce decides the collective early exit. `fr` / `bk` are the child's
+// front / back schedules (LDS rows, runtime-indexed by the pair's machines;
+// bk is the min_tails row under forward branching), `sched` its scheduled-job
+// mask. LDS supplies jp (round-0 pair rows), pair1 / pair2 and JP_LDS. Returns
+// the wave-wide max: the exact bound when `exited` stays false, otherwise some
+// partial max > best.
+template <int MM, class LDS, class BackT>
+__device__ inline int wave_lb2_sweep(const LDS& lds, const PfspDevTables& tb,
+                                     const uint16_t* fr, const BackT* bk, uint32_t sched,
+                                     int jobs, int best, int lane, bool& exited) {
+  constexpr int PAIRS = MM * (MM - 1) / 2;
+  constexpr int ROUNDS = (PAIRS + 63) / 64;
+  int mylb = 0;
+#pragma unroll
+  for (int r = 0; r < ROUNDS; r++) {
+    if (!exited) {
+      const int pr = lane + r * 64;
+      if (pr < PAIRS) {
+        const int ma0 = lds.pair1[pr];
+        const int ma1 = lds.pair2[pr];
+        int t0 = fr[ma0];
+        int t1 = fr[ma1];
+        const uint32_t* jp =
+            (pr < LDS::JP_LDS) ? &lds.jp[pr * jobs] : &tb.johnson_packed_w[pr * jobs];
+        // jobs == MAX_JOBS for every GPU-supported Taillard instance:
+        // full unrolling lets the compiler batch the 20 dependent
+        // ds_read_b32s instead of serializing load->use 20 times
+        if (jobs == MAX_JOBS) {
+#pragma unroll
+          for (int j = 0; j < MAX_JOBS; j++) {
+            const uint32_t v = jp[j];
+            const int job = static_cast<int>(v >> 27);
+            if (!(sched >> job & 1u)) {
+              t0 += static_cast<int>(v & 0xffu);
+              t1 = max(t1, t0 + static_cast<int>((v >> 16) & 0x7ffu));
+              t1 += static_cast<int>((v >> 8) & 0xffu);
+            }
+          }
+        } else {
+          for (int j = 0; j < jobs; j++) {
+            const uint32_t v = jp[j];
+            const int job = static_cast<int>(v >> 27);
+            if (!(sched >> job & 1u)) {
+              t0 += static_cast<int>(v & 0xffu);
+              t1 = max(t1, t0 + static_cast<int>((v >> 16) & 0x7ffu));
+              t1 += static_cast<int>((v >> 8) & 0xffu);
+            }
+          }
+        }
+        mylb = max(mylb, max(t1 + static_cast<int>(bk[ma1]), t0 + static_cast<int>(bk[ma0])));
+      }
+      if (wave_max_i32(mylb) > best) exited = true;  // collective early exit
+    }
+  }
+  return wave_max_i32(mylb);
+}
+
 template <int MM>
 __global__ void k_pfsp_x_lb2w(DevCtl* ctl, const PFSPNode* pool, PFSPNode* childbuf,
                               uint32_t* waveCounts, unsigned long long* waveSols, int jobs,
@@ -1198,52 +1257,8 @@ __global__ void k_pfsp_x_lb2w(DevCtl* ctl, const PFSPNode* pool, PFSPNode* child
     const int lp = lds.lpar[ct];
     const uint32_t sched = lds.pmask[lp] | (1u << lds.snodes[lp].prmu[k]);
 
-    int mylb = 0;
     bool exited = false;
-    constexpr int ROUNDS = (PAIRS + 63) / 64;
-#pragma unroll
-    for (int r = 0; r < ROUNDS; r++) {
-      if (!exited) {
-        const int pr = lane + r * 64;
-        if (pr < PAIRS) {
-          const int ma0 = lds.pair1[pr];
-          const int ma1 = lds.pair2[pr];
-          int t0 = fr[ma0];
-          int t1 = fr[ma1];
-          const uint32_t* jp = (pr < LdsLb2w<MM>::JP_LDS)
-                                   ? &lds.jp[pr * jobs]
-                                   : &tb.johnson_packed_w[pr * jobs];
-          // jobs == MAX_JOBS for every GPU-supported Taillard instance:
-          // full unrolling lets the compiler batch the 20 dependent
-          // ds_read_b32s instead of serializing load->use 20 times
-          if (jobs == MAX_JOBS) {
-#pragma unroll
-            for (int j = 0; j < MAX_JOBS; j++) {
-              const uint32_t v = jp[j];
-              const int job = static_cast<int>(v >> 27);
-              if (!(sched >> job & 1u)) {
-                t0 += static_cast<int>(v & 0xffu);
-                t1 = max(t1, t0 + static_cast<int>((v >> 16) & 0x7ffu));
-                t1 += static_cast<int>((v >> 8) & 0xffu);
-              }
-            }
-          } else {
-            for (int j = 0; j < jobs; j++) {
-              const uint32_t v = jp[j];
-              const int job = static_cast<int>(v >> 27);
-              if (!(sched >> job & 1u)) {
-                t0 += static_cast<int>(v & 0xffu);
-                t1 = max(t1, t0 + static_cast<int>((v >> 16) & 0x7ffu));
-                t1 += static_cast<int>((v >> 8) & 0xffu);
-              }
-            }
-          }
-          mylb = max(mylb, max(t1 + lds.min_tails[ma1], t0 + lds.min_tails[ma0]));
-        }
-        if (wave_max_i32(mylb) > best) exited = true;  // collective early exit
-      }
-    }
-    const int lb = wave_max_i32(mylb);
+    const int lb = wave_lb2_sweep<MM>(lds, tb, fr, lds.min_tails, sched, jobs, best, lane, exited);
     if (lane == 0) {
       if (leaf) {
         mysols++;
@@ -1262,6 +1277,268 @@ __global__ void k_pfsp_x_lb2w(DevCtl* ctl, const PFSPNode* pool, PFSPNode* child
   }
 }
 
+
+// ---------------------------------------------------------------------------
+// lb12: lb1_d picks the direction and filters the children (one thread per
+// parent), lb2 refines only the survivors (one wave per survivor). Few
+// children pass the filter (1.2-1.6 per parent on ta0xx with ub=1), so the
+// survivors of a whole block go through one LDS queue and the waves take
+// queue entries round-robin: the Johnson sweep runs on a dense set however
+// unevenly the survivors are spread over the parents.
+//
+// lb1_d bounds a child from the PARENT's front / back, which are min_heads /
+// min_tails where nothing is fixed; lb2 bounds the CHILD, whose changed side
+// is one add_forward / add_backward step from ZEROS in that case. The rows
+// phase 1 leaves in LDS are therefore the ones a child starts from: zeros on
+// the side the parent's direction extends when nothing is fixed there, the
+// lb1_d schedule (min_heads / min_tails included) on the other side.
+// ---------------------------------------------------------------------------
+template <int MM>
+struct LdsLb12 {
+  static constexpr int PAIRS = MM * (MM - 1) / 2;
+  static constexpr int JP_LDS = PAIRS < 64 ? PAIRS : 64;  // as LdsLb2w: round-0 rows only
+  LdsLb1Bi<MM> b1;
+  uint32_t jp[JP_LDS * MAX_JOBS];
+  uint8_t pair1[PAIRS], pair2[PAIRS];
+  alignas(8) PFSPNode snodes[BLOCK];
+  uint16_t fronts[BLOCK][MM + 1];  // per parent (values <= 20*20*99)
+  uint16_t backs[BLOCK][MM + 1];
+  uint32_t mask[BLOCK];  // jobs fixed at the front or at the back
+  uint8_t dir[BLOCK];    // 0 front, 1 back
+  // lb1_d survivors of the block in parent order, then position order:
+  // parent << 8 | k; phase 2 sets LB12_PRUNED where lb2 prunes
+  uint16_t queue[BLOCK * MAX_JOBS];
+  uint16_t wrow[BLOCK / 64][MM + 2];  // a wave's current child: its changed side
+};
+constexpr uint16_t LB12_PRUNED = 0x80;
+
+template <int MM>
+__device__ inline void stage_lb12_tables(LdsLb12<MM>& lds, const PfspDevTables& tb, int jobs) {
+  stage_lb1bi_tables<MM>(lds.b1, tb, jobs);
+  for (int i = threadIdx.x; i < LdsLb12<MM>::JP_LDS * jobs; i += blockDim.x)
+    lds.jp[i] = tb.johnson_packed_w[i];
+  if (threadIdx.x < LdsLb12<MM>::PAIRS) {
+    lds.pair1[threadIdx.x] = tb.pairs1_w[threadIdx.x];
+    lds.pair2[threadIdx.x] = tb.pairs2_w[threadIdx.x];
+  }
+}
+
+// What phase 1 found out about this thread's parent.
+struct Lb12Parent {
+  int depth = 0, limit1 = 0, limit2 = 0;
+  bool bwd = false, leaf = false;
+  int leaf_min = 0x7fffffff;  // leaf parent: min lb1_d value of the chosen direction
+  uint32_t nsurv = 0;         // children passing the lb1_d filter (0 for a leaf)
+  uint32_t qpos = 0;          // its first queue entry
+};
+
+// Phase 1, every thread of the block (lp < 0: no parent): lb1_d setup, pass 1
+// and the direction as in k_pfsp_x_lb1d_bi; rows, mask and direction to LDS;
+// pass 2 appends the survivors to the queue at the position an exclusive scan
+// of the survivor counts gives (no atomics: the queue order is parent order,
+// then position order). on_b1(k, b1) sees every child that gets no lb2: a
+// leaf's children and the ones the filter pruned. Returns the queue length;
+// ends with a block barrier.
+template <int MM, class OnB1>
+__device__ inline uint32_t lb12_phase1(LdsLb12<MM>& lds, int lp, int jobs, int best, int br,
+                                       Lb12Parent& P, OnB1&& on_b1) {
+  int front[MM], back[MM], remain[MM];
+  if (lp >= 0) {
+    const PFSPNode& p = lds.snodes[lp];
+    P.depth = p.depth;
+    P.limit1 = p.limit1;
+    P.limit2 = jobs - p.nback;
+    P.leaf = P.depth + 1 == jobs;
+    lb1d_bi_setup<MM>(lds.b1, p.prmu, P.limit1, P.limit2, jobs, front, back, remain);
+    const bool dyn = br == 3;
+    P.bwd = br == 1 || (br == 2 && (P.depth & 1));
+    int cntF = 0, cntB = 0, sumF = 0, sumB = 0;
+    int minF = 0x7fffffff, minB = 0x7fffffff;
+    for (int k = P.limit1 + 1; k < P.limit2; k++) {
+      const int job = p.prmu[k];
+      if (dyn || !P.bwd) {
+        const int lb = lb1d_bound_front<MM>(lds.b1, front, back, remain, job, jobs);
+        cntF += lb < best;
+        sumF += lb;
+        minF = min(minF, lb);
+      }
+      if (dyn || P.bwd) {
+        const int lb = lb1d_bound_back<MM>(lds.b1, front, back, remain, job, jobs);
+        cntB += lb < best;
+        sumB += lb;
+        minB = min(minB, lb);
+      }
+    }
+    if (dyn) P.bwd = cntB < cntF || (cntB == cntF && sumB > sumF);
+    P.leaf_min = P.bwd ? minB : minF;
+    if (!P.leaf) P.nsurv = static_cast<uint32_t>(P.bwd ? cntB : cntF);
+    uint32_t sched = 0;
+    for (int i = 0; i <= P.limit1; i++) sched |= 1u << p.prmu[i];
+    for (int i = P.limit2; i < jobs; i++) sched |= 1u << p.prmu[i];
+    lds.mask[lp] = sched;
+    lds.dir[lp] = P.bwd ? 1 : 0;
+    const bool zero_front = !P.bwd && P.limit1 == -1;
+    const bool zero_back = P.bwd && P.limit2 == jobs;
+#pragma unroll
+    for (int j = 0; j < MM; j++) {
+      lds.fronts[lp][j] = static_cast<uint16_t>(zero_front ? 0 : front[j]);
+      lds.backs[lp][j] = static_cast<uint16_t>(zero_back ? 0 : back[j]);
+    }
+  }
+  uint32_t Q;
+  P.qpos = block_excl_scan(P.nsurv, Q);
+  if (lp >= 0) {
+    const PFSPNode& p = lds.snodes[lp];
+    uint32_t q = P.qpos;
+    for (int k = P.limit1 + 1; k < P.limit2; k++) {
+      const int job = p.prmu[k];
+      const int b1 = P.bwd ? lb1d_bound_back<MM>(lds.b1, front, back, remain, job, jobs)
+                           : lb1d_bound_front<MM>(lds.b1, front, back, remain, job, jobs);
+      if (!P.leaf && b1 < best)
+        lds.queue[q++] = static_cast<uint16_t>(lp << 8 | k);
+      else
+        on_b1(k, b1);
+    }
+  }
+  __syncthreads();
+  return Q;
+}
+
+// Phase 2: the block's waves take queue entries round-robin. One O(m) step
+// from the parent's row makes the child's changed side (a wave-private LDS
+// row: the sweep indexes it by the pair's machines), the other side is the
+// parent's row, and the lanes sweep the pairs 64 per round. Lane 0 hands
+// done(entry, parent, k, lb2, keep) the outcome; lb2 is exact unless the
+// collective exit fired (then it is some value > best).
+template <int MM, class Done>
+__device__ inline void lb12_phase2(LdsLb12<MM>& lds, const PfspDevTables& tb, uint32_t Q,
+                                   int jobs, int best, Done&& done) {
+  const int wid = threadIdx.x >> 6;
+  const int lane = threadIdx.x & 63;
+  uint16_t* row = lds.wrow[wid];
+  for (uint32_t e = wid; e < Q; e += BLOCK / 64) {
+    const uint32_t ent = lds.queue[e];  // same address across the wave: broadcast
+    const int lp = static_cast<int>(ent >> 8);
+    const int k = static_cast<int>(ent & 0x7fu);
+    const int job = lds.snodes[lp].prmu[k];
+    const bool bwd = lds.dir[lp] != 0;
+    if (!bwd) {  // add_forward
+      const uint16_t* pf = lds.fronts[lp];
+      int prev = pf[0] + lds.b1.p[job];
+      if (lane == 0) row[0] = static_cast<uint16_t>(prev);
+#pragma unroll
+      for (int j = 1; j < MM; j++) {
+        prev = max(prev, static_cast<int>(pf[j])) + lds.b1.p[j * jobs + job];
+        if (lane == 0) row[j] = static_cast<uint16_t>(prev);
+      }
+    } else {  // add_backward
+      const uint16_t* pb = lds.backs[lp];
+      int prev = pb[MM - 1] + lds.b1.p[(MM - 1) * jobs + job];
+      if (lane == 0) row[MM - 1] = static_cast<uint16_t>(prev);
+#pragma unroll
+      for (int jj = 0; jj < MM - 1; jj++) {
+        const int j = MM - 2 - jj;
+        prev = max(prev, static_cast<int>(pb[j])) + lds.b1.p[j * jobs + job];
+        if (lane == 0) row[j] = static_cast<uint16_t>(prev);
+      }
+    }
+    // lane 0 wrote the row the whole wave reads next: order this wave's LDS traffic
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_wave_barrier();
+    const uint32_t sched = lds.mask[lp] | (1u << job);
+    const uint16_t* fr = bwd ? lds.fronts[lp] : row;
+    const uint16_t* bk = bwd ? row : lds.backs[lp];
+    bool exited = false;
+    const int lb = wave_lb2_sweep<MM>(lds, tb, fr, bk, sched, jobs, best, lane, exited);
+    if (lane == 0) done(e, lp, k, lb, !exited && lb < best);
+    // the next entry overwrites the row: every lane's reads of it come first
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_wave_barrier();
+  }
+}
+
+// K1 for PFSP lb12, geometry code 4 = the lb1_d geometry: one parent per
+// thread, grid ceil(M / BLOCK), one BLOCK*MAX_JOBS slab and one count per
+// block, so k_presum / k_gather2 see the contract of code 0. br: 0 fwd, 1 bwd,
+// 2 alt, 3 minbranch. `best` is the snapshot read at kernel start; only leaves
+// atomicMin into ctl->best.
+template <int MM>
+__global__ void k_pfsp_x_lb12(DevCtl* ctl, const PFSPNode* pool, PFSPNode* childbuf,
+                              uint32_t* blockCounts, unsigned long long* blockSols, int jobs,
+                              PfspDevTables tb, unsigned long long m, unsigned long long M,
+                              int br) {
+  __shared__ LdsLb12<MM> lds;
+  stage_lb12_tables<MM>(lds, tb, jobs);
+  const unsigned long long c = derive_chunk(ctl, m, M);
+  const PFSPNode* parents = pool + (ctl->size - c);
+  const unsigned long long t =
+      static_cast<unsigned long long>(blockIdx.x) * blockDim.x + threadIdx.x;
+  const int lp = stage_parents(parents, c, 1, lds.snodes, t);
+  __syncthreads();
+  const int best = ctl->best;
+
+  Lb12Parent P;
+  const uint32_t Q = lb12_phase1<MM>(lds, lp, jobs, best, br, P, [](int, int) {});
+  unsigned long long sols = 0;
+  if (lp >= 0 && P.leaf) {
+    sols = static_cast<unsigned long long>(P.limit2 - (P.limit1 + 1));
+    if (sols > 0 && P.leaf_min < best) atomicMin(&ctl->best, P.leaf_min);
+  }
+  lb12_phase2<MM>(lds, tb, Q, jobs, best, [&](uint32_t e, int, int, int, bool keep) {
+    if (!keep) lds.queue[e] |= LB12_PRUNED;
+  });
+  __syncthreads();
+
+  // phase 3: rank the kept children by a second scan, in queue order
+  uint32_t cnt = 0;
+  for (uint32_t e = P.qpos; e < P.qpos + P.nsurv; e++) cnt += !(lds.queue[e] & LB12_PRUNED);
+  uint32_t totC;
+  const uint32_t pre = block_excl_scan(cnt, totC);
+  const unsigned long long totS = block_reduce_u64(sols);
+  if (threadIdx.x == 0) {
+    blockCounts[blockIdx.x] = totC;
+    blockSols[blockIdx.x] = totS;
+  }
+  if (cnt > 0) {
+    unsigned long long slot =
+        static_cast<unsigned long long>(blockIdx.x) * (BLOCK * MAX_JOBS) + pre;
+    const PFSPNode& p = lds.snodes[lp];
+    for (uint32_t e = P.qpos; e < P.qpos + P.nsurv; e++) {
+      const uint32_t ent = lds.queue[e];
+      if (ent & LB12_PRUNED) continue;
+      const int k = static_cast<int>(ent & 0x7fu);
+      if (P.bwd)
+        emit_pfsp_child_back(childbuf, slot++, p, P.depth, jobs - P.limit2, jobs, k);
+      else
+        emit_pfsp_child_front(childbuf, slot++, p, P.depth, P.limit1, k);
+    }
+  }
+}
+
+// lb12 hostpool / test kernel: phases 1-2 of the expand, outcomes written out
+// instead of children. dir[n]: 0 front, 1 back. bounds[n * jobs] by position:
+// untouched outside the unscheduled range (callers preset -1), the lb1_d value
+// for a leaf's children and for the ones the filter pruned, else the lb2 value
+// (exact when <= best; any value > best once the collective exit fired).
+template <int MM>
+__global__ void k_pfsp_eval_lb12(const PFSPNode* parents, int n, int jobs, PfspDevTables tb,
+                                 int best, int br, uint8_t* dir, int32_t* bounds) {
+  __shared__ LdsLb12<MM> lds;
+  stage_lb12_tables<MM>(lds, tb, jobs);
+  const unsigned long long t =
+      static_cast<unsigned long long>(blockIdx.x) * blockDim.x + threadIdx.x;
+  const int lp = stage_parents(parents, static_cast<unsigned long long>(n), 1, lds.snodes, t);
+  __syncthreads();
+  Lb12Parent P;
+  int32_t* mine = bounds + t * jobs;
+  const uint32_t Q =
+      lb12_phase1<MM>(lds, lp, jobs, best, br, P, [&](int k, int b1) { mine[k] = b1; });
+  if (lp >= 0) dir[t] = P.bwd ? 1 : 0;
+  int32_t* blk = bounds + static_cast<unsigned long long>(blockIdx.x) * blockDim.x * jobs;
+  lb12_phase2<MM>(lds, tb, Q, jobs, best, [&](uint32_t, int lp2, int k, int lb, bool) {
+    blk[lp2 * jobs + k] = lb;
+  });
+}
 
 // Per-256-entry group sums of the wave counts: with per-WAVE count granularity
 // (lb2's G ~ 15k at M = 50000) the gather blocks' linear prefix walk costs
@@ -1365,8 +1642,11 @@ void launch_nq_eval(const NQNode* parents, int n, int N, int g, uint8_t* labels,
 template <int MM>
 static void launch_pfsp_eval_mm(const PFSPNode* parents, int n, int jobs, int lbk,
                                 const PfspDevTables& tb, int best, int32_t* bounds,
-                                hipStream_t s, int br, int32_t* bounds_end) {
-  if (br != 0) {  // lb1_d in both directions (launch_pfsp_eval rejects other bounds)
+                                hipStream_t s, int br, int32_t* bounds_end, uint8_t* dir) {
+  if (lbk == 4) {  // lb12: thread per parent, then wave per lb1_d survivor
+    hipLaunchKernelGGL((k_pfsp_eval_lb12<MM>), dim3(grid_for(n)), dim3(BLOCK), 0, s, parents,
+                       n, jobs, tb, best, br, dir, bounds);
+  } else if (br != 0) {  // lb1_d in both directions (launch_pfsp_eval rejects other bounds)
     hipLaunchKernelGGL((k_pfsp_eval_lb1d_bi<MM>), dim3(grid_for(n)), dim3(BLOCK), 0, s,
                        parents, n, jobs, tb, bounds, bounds_end);
   } else if (lbk == 0) {  // lb1_d: thread per parent
@@ -1385,16 +1665,18 @@ static void launch_pfsp_eval_mm(const PFSPNode* parents, int n, int jobs, int lb
 
 void launch_pfsp_eval(const PFSPNode* parents, int n, int jobs, int machines, int lbk,
                       const PfspDevTables& tb, int best, int32_t* bounds, hipStream_t s,
-                      int br, int32_t* bounds_end) {
-  if (br != 0 && (lbk != 0 || bounds_end == nullptr))
+                      int br, int32_t* bounds_end, uint8_t* dir) {
+  if (lbk == 4 && dir == nullptr)
+    throw std::invalid_argument("launch_pfsp_eval: lb12 needs a dir buffer");
+  if (lbk != 4 && br != 0 && (lbk != 0 || bounds_end == nullptr))
     throw std::invalid_argument(
         "launch_pfsp_eval: a non-fwd branching rule needs lb1_d and a bounds_end buffer");
   if (machines == 5)
-    launch_pfsp_eval_mm<5>(parents, n, jobs, lbk, tb, best, bounds, s, br, bounds_end);
+    launch_pfsp_eval_mm<5>(parents, n, jobs, lbk, tb, best, bounds, s, br, bounds_end, dir);
   else if (machines == 10)
-    launch_pfsp_eval_mm<10>(parents, n, jobs, lbk, tb, best, bounds, s, br, bounds_end);
+    launch_pfsp_eval_mm<10>(parents, n, jobs, lbk, tb, best, bounds, s, br, bounds_end, dir);
   else
-    launch_pfsp_eval_mm<20>(parents, n, jobs, lbk, tb, best, bounds, s, br, bounds_end);
+    launch_pfsp_eval_mm<20>(parents, n, jobs, lbk, tb, best, bounds, s, br, bounds_end, dir);
 }
 
 // ---- devpool v3 launchers ----
@@ -1405,6 +1687,7 @@ void launch_pfsp_eval(const PFSPNode* parents, int n, int jobs, int machines, in
 // machine pairs the wave-cooperative kernel leaves most of a wave idle and
 // its collective early exit buys little, while the per-lane full sweep is a
 // short fully-unrolled register loop (ta005 20x5 measured 3x faster).
+// 4 = lb12: the lb1_d geometry (thread per parent, per-block slabs and counts).
 int devpool_lbk_geom(int lbk, int machines) {
   if (lbk != 2) return lbk;
   // per-lane for m=5 (10 pairs: the wave kernel idles 54/64 lanes, ta005
@@ -1416,7 +1699,7 @@ int devpool_lbk_geom(int lbk, int machines) {
 }
 
 int devpool_grid(unsigned long long M, int per, int lbk) {
-  if (lbk == 0)  // lb1_d: one thread per parent
+  if (lbk == 0 || lbk == 4)  // lb1_d, lb12: one thread per parent
     return static_cast<int>((M + BLOCK - 1) / BLOCK);
   if (lbk == 2)  // wave-cooperative lb2: counts/slabs are per WAVE (64 slots),
                  // padded to whole 4-wave blocks (gw index = blockIdx*4 + wid)
@@ -1425,7 +1708,7 @@ int devpool_grid(unsigned long long M, int per, int lbk) {
 }
 
 int devpool_stride(int lbk) {
-  if (lbk == 0) return BLOCK * MAX_JOBS;
+  if (lbk == 0 || lbk == 4) return BLOCK * MAX_JOBS;
   if (lbk == 2) return 64;  // one wave's child slab
   return EMIT_TILE;
 }
@@ -1449,7 +1732,10 @@ static void launch_pfsp_x_mm(DevCtl* ctl, const PFSPNode* pool, PFSPNode* childb
                              uint32_t* bc, unsigned long long* bs, int jobs, int lbk,
                              const PfspDevTables& tb, unsigned long long m,
                              unsigned long long M, hipStream_t s, int br) {
-  if (br != 0) {  // lb1_d geometry (code 0), both-directions kernel
+  if (lbk == 4) {  // lb12, every branching rule
+    hipLaunchKernelGGL((k_pfsp_x_lb12<MM>), dim3(devpool_grid(M, jobs, 4)), dim3(BLOCK), 0, s,
+                       ctl, pool, childbuf, bc, bs, jobs, tb, m, M, br);
+  } else if (br != 0) {  // lb1_d geometry (code 0), both-directions kernel
     hipLaunchKernelGGL((k_pfsp_x_lb1d_bi<MM>), dim3(devpool_grid(M, jobs, 0)), dim3(BLOCK), 0,
                        s, ctl, pool, childbuf, bc, bs, jobs, tb, m, M, br);
   } else if (lbk == 0) {
@@ -1473,8 +1759,8 @@ void launch_pfsp_x(DevCtl* ctl, const PFSPNode* pool, PFSPNode* childbuf, uint32
                    unsigned long long* bs, int jobs, int machines, int lbk,
                    const PfspDevTables& tb,
                    unsigned long long m, unsigned long long M, hipStream_t s, int br) {
-  if (br != 0 && lbk != 0)
-    throw std::invalid_argument("launch_pfsp_x: a non-fwd branching rule needs lb1_d");
+  if (br != 0 && lbk != 0 && lbk != 4)
+    throw std::invalid_argument("launch_pfsp_x: a non-fwd branching rule needs lb1_d or lb12");
   if (machines == 5)
     launch_pfsp_x_mm<5>(ctl, pool, childbuf, bc, bs, jobs, lbk, tb, m, M, s, br);
   else if (machines == 10)

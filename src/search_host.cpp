@@ -20,7 +20,8 @@ LbKind lb_from_string(const std::string& s) {
   if (s == "lb1") return LbKind::LB1;
   if (s == "lb1_d") return LbKind::LB1_D;
   if (s == "lb2") return LbKind::LB2;
-  throw std::invalid_argument("unsupported lower bound '" + s + "' (lb1, lb1_d, lb2)");
+  if (s == "lb12") return LbKind::LB12;
+  throw std::invalid_argument("unsupported lower bound '" + s + "' (lb1, lb1_d, lb2, lb12)");
 }
 
 Branching branching_from_string(const std::string& s) {
@@ -46,7 +47,7 @@ const char* branching_name(Branching br) {
 }
 
 void check_branching_supported(LbKind lb, Branching br, bool gpu_tier) {
-  if (br == Branching::FWD) return;
+  if (br == Branching::FWD || lb == LbKind::LB12) return;  // lb12: every rule, seq and gpu
   const char* lbn = lb == LbKind::LB1 ? "lb1" : (lb == LbKind::LB1_D ? "lb1_d" : "lb2");
   if (br == Branching::MINBRANCH && lb != LbKind::LB1_D)
     throw std::invalid_argument(std::string("branching rule 'minbranch' with bound '") + lbn +
@@ -367,10 +368,64 @@ void decompose_bi(const PfspInstance& I, LbKind lb, const PFSPNode& parent, uint
   }
 }
 
+// lb12: lb1_d picks the direction and filters the children, lb2 refines the
+// survivors (evaluated against the incumbent, never at leaves).
+void decompose_lb12(const PfspInstance& I, const PFSPNode& parent, uint64_t& tree,
+                    uint64_t& sol, int& best, Pool<PFSPNode>& pool) {
+  const int jobs = I.jobs;
+  uint8_t dir;
+  int32_t b[MAX_JOBS];
+  pfsp_lb12_eval(I, parent, best, dir, b);
+  const bool leaf = parent.depth + 1 == jobs;
+  for (int i = parent.limit1 + 1; i < jobs - parent.nback; i++) {
+    if (leaf) {
+      sol += 1;
+      if (b[i] < best) best = b[i];
+    } else if (b[i] < best) {
+      pool.pushBack(dir ? make_child_back(parent, jobs, i) : make_child_front(parent, i));
+      tree += 1;
+    }
+  }
+}
+
 }  // namespace
+
+void pfsp_lb12_eval(const PfspInstance& I, const PFSPNode& parent, int best, uint8_t& dir,
+                    int32_t* bounds) {
+  const int jobs = I.jobs;
+  const int limit1 = parent.limit1, limit2 = jobs - parent.nback;
+  const bool leaf = parent.depth + 1 == jobs;
+  int lb_begin[MAX_JOBS], lb_end[MAX_JOBS];
+  bool back;
+  if (I.br == Branching::MINBRANCH) {
+    lb1_children_bounds_bi(I.lb1, parent.prmu, limit1, limit2, lb_begin, lb_end);
+    back = choose_minbranch(
+        limit1 + 1, limit2, best, [&](int k) { return lb_begin[parent.prmu[k]]; },
+        [&](int k) { return lb_end[parent.prmu[k]]; });
+  } else {
+    back = static_backward(I.br, parent.depth);
+    lb1_children_bounds_bi(I.lb1, parent.prmu, limit1, limit2, back ? nullptr : lb_begin,
+                           back ? lb_end : nullptr);
+  }
+  dir = back ? 1 : 0;
+  for (int i = 0; i < jobs; i++) bounds[i] = -1;
+  for (int i = limit1 + 1; i < limit2; i++) {
+    const int b1 = (back ? lb_end : lb_begin)[parent.prmu[i]];
+    if (leaf || b1 >= best) {  // leaves keep the lb1_d rule; a filtered child costs no lb2
+      bounds[i] = b1;
+      continue;
+    }
+    const PFSPNode child = back ? make_child_back(parent, jobs, i) : make_child_front(parent, i);
+    bounds[i] = lb2_bound(I.lb1, I.lb2, child.prmu, child.limit1, jobs - child.nback, best);
+  }
+}
 
 void pfsp_decompose(const PfspInstance& I, LbKind lb, const PFSPNode& parent, uint64_t& tree,
                     uint64_t& sol, int& best, Pool<PFSPNode>& pool) {
+  if (lb == LbKind::LB12) {
+    decompose_lb12(I, parent, tree, sol, best, pool);
+    return;
+  }
   if (I.br != Branching::FWD) {
     decompose_bi(I, lb, parent, tree, sol, best, pool);
     return;
@@ -385,6 +440,8 @@ void pfsp_decompose(const PfspInstance& I, LbKind lb, const PFSPNode& parent, ui
     case LbKind::LB2:
       decompose_lb2(I, parent, tree, sol, best, pool);
       break;
+    case LbKind::LB12:
+      break;  // handled above
   }
 }
 
@@ -452,6 +509,27 @@ void pfsp_generate_children_bi(const PfspInstance& I, const PFSPNode* parents, s
     const bool leaf = parent.depth + 1 == jobs;
     for (int j = lo; j < hi; j++) {
       const int lb = back ? b[j] : f[j];
+      if (leaf) {
+        sol += 1;
+        if (lb < best) best = lb;
+      } else if (lb < best) {
+        pool.pushBack(back ? make_child_back(parent, jobs, j) : make_child_front(parent, j));
+        tree += 1;
+      }
+    }
+  }
+}
+
+void pfsp_generate_children_lb12(const PfspInstance& I, const PFSPNode* parents, size_t n,
+                                 const uint8_t* dir, const int32_t* bounds, uint64_t& tree,
+                                 uint64_t& sol, int& best, Pool<PFSPNode>& pool) {
+  const int jobs = I.jobs;
+  for (size_t i = 0; i < n; i++) {
+    const PFSPNode& parent = parents[i];
+    const bool back = dir[i] != 0;
+    const bool leaf = parent.depth + 1 == jobs;
+    for (int j = parent.limit1 + 1; j < jobs - parent.nback; j++) {
+      const int lb = bounds[i * jobs + j];
       if (leaf) {
         sol += 1;
         if (lb < best) best = lb;

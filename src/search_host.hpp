@@ -35,7 +35,9 @@ struct Result {
                                      // nqueens_multigpu_chpl.chpl:337)
 };
 
-enum class LbKind { LB1, LB1_D, LB2 };
+// LB12 is the two-stage bound: lb1_d picks the branching direction and filters
+// the children, lb2 (Johnson) then bounds only the survivors.
+enum class LbKind { LB1, LB1_D, LB2, LB12 };
 LbKind lb_from_string(const std::string& s);
 
 // ---------------- N-Queens ----------------
@@ -74,15 +76,16 @@ void nq_bfs_level(int N, int g, size_t target, Pool<NQNode>& pool, uint64_t& tre
 //   FWD        always the front (the reference's tree; the default)
 //   BWD        always the back
 //   ALT        front when the parent's depth is even, back when odd
-//   MINBRANCH  (lb1_d only) the side with fewer children surviving the
-//              incumbent; on a tie the side with the larger bound sum
+//   MINBRANCH  (lb1_d and lb12) the side with fewer children surviving the
+//              incumbent under lb1_d; on a tie the side with the larger bound sum
 enum class Branching { FWD = 0, BWD = 1, ALT = 2, MINBRANCH = 3 };
 Branching branching_from_string(const std::string& s);
 const char* branching_name(Branching br);
 // Throws std::invalid_argument naming the combination when `lb` has no
 // implementation of `br` (minbranch needs both directions' bounds of every
 // child, which only lb1_d produces in one pass). gpu_tier adds the GPU tier's
-// restriction: its bi-directional kernels exist for lb1_d only.
+// restriction: its bi-directional kernels exist for lb1_d only. lb12 has its
+// own decompose rule and kernels and takes every rule on both tiers.
 void check_branching_supported(LbKind lb, Branching br, bool gpu_tier);
 
 // A pool handed in from outside (the *_from_pool entry points): under fwd the
@@ -129,6 +132,21 @@ void pfsp_generate_children_bi(const PfspInstance& I, const PFSPNode* parents, s
                                const int32_t* lb_begin, const int32_t* lb_end,
                                uint64_t& tree, uint64_t& sol, int& best,
                                Pool<PFSPNode>& pool);
+
+// lb12 for one parent (the definition the kernels are tested against): the
+// direction (0 front, 1 back) chosen by I.br on the lb1_d values, and per
+// POSITION -1 outside the unscheduled range, the lb1_d value of the chosen
+// direction for a leaf's children and for children with lb1_d >= best, and
+// otherwise lb2_bound of the child (early exit: exact when <= best).
+void pfsp_lb12_eval(const PfspInstance& I, const PFSPNode& parent, int best, uint8_t& dir,
+                    int32_t* bounds);
+
+// Hostpool, lb12: dir[i] / bounds[i*jobs + j] as pfsp_lb12_eval lays them out,
+// evaluated on the GPU with the batch's incumbent (>= the live one, so a
+// value that pruned there prunes here too).
+void pfsp_generate_children_lb12(const PfspInstance& I, const PFSPNode* parents, size_t n,
+                                 const uint8_t* dir, const int32_t* bounds, uint64_t& tree,
+                                 uint64_t& sol, int& best, Pool<PFSPNode>& pool);
 
 // N-Queens variant from GPU safety labels (nqueens_gpu_chpl.chpl:126-149).
 void nq_generate_children(const NQNode* parents, size_t n, int N, const uint8_t* labels,
