@@ -9,6 +9,7 @@
 #include "engine_gpu.hpp"
 #include "gpu_api.hpp"
 #include "nodes.hpp"
+#include "nq_finish.hpp"
 #include "pool.hpp"
 #include "search_host.hpp"
 #include "taillard.hpp"
@@ -58,6 +59,38 @@ std::vector<NodeT> nodes_from_bytes(const py::bytes& b) {
   std::vector<NodeT> v(s.size() / sizeof(NodeT));
   std::memcpy(v.data(), s.data(), s.size());
   return v;
+}
+
+// CPU run of the k_nq_x finisher's loop (nq_finish.hpp) over one job: the
+// nodes and solutions below the state (cols, d1, d2) whose first empty row is
+// `row`. Jobs of up to 8 rows go through the kernel's own instantiation.
+template <int LEVELS>
+py::tuple nq_finish_count(uint32_t cols, uint32_t d1, uint32_t d2, int row, int N) {
+  NqFlat<LEVELS> st;
+  st.tree = 0;
+  st.sol = 0;
+  const uint32_t msk = (1u << N) - 1u;
+  bool handed = false;
+  nq_flat_run<LEVELS, true>(
+      st,
+      [&](NqFlat<LEVELS>& w) {
+        if (handed) return false;
+        handed = true;
+        w.template load<true>(cols, d1, d2, row, N, msk, 1);
+        return true;
+      },
+      msk, 1);
+  return py::make_tuple(static_cast<uint64_t>(st.tree), static_cast<uint64_t>(st.sol));
+}
+
+py::tuple nq_finish_count_cpu(uint32_t cols, uint32_t d1, uint32_t d2, int row, int N) {
+  if (N < 1 || N > MAX_JOBS) throw std::invalid_argument("N must be in 1..20");
+  const int rows = N - row;
+  if (row < 0 || rows < 1 || rows > NQ_FLAT_LEVELS_MAX)
+    throw std::invalid_argument("the job needs 1..12 empty rows");
+  if ((cols | d1 | d2) >> N) throw std::invalid_argument("mask bits at or above column N");
+  return rows <= NQ_FLAT_LEVELS_DEV ? nq_finish_count<NQ_FLAT_LEVELS_DEV>(cols, d1, d2, row, N)
+                                    : nq_finish_count<NQ_FLAT_LEVELS_MAX>(cols, d1, d2, row, N);
 }
 
 template <typename NodeT>
@@ -574,6 +607,8 @@ PYBIND11_MODULE(_core, mod) {
           py::arg("device") = 0, py::arg("br") = "fwd");
 
   mod.def("nq_cpu_labels", &nq_cpu_labels);
+  mod.def("nq_finish_count_cpu", &nq_finish_count_cpu, py::arg("cols"), py::arg("d1"),
+          py::arg("d2"), py::arg("row"), py::arg("N"));
   mod.def("pfsp_cpu_bounds", &pfsp_cpu_bounds);
   mod.def("pfsp_cpu_bounds_bi", &pfsp_cpu_bounds_bi, py::arg("inst"), py::arg("nodes"));
   mod.def("pfsp_gpu_bounds_bi",

@@ -159,6 +159,7 @@ DevpoolStepCtl devpool_step(const Problem& problem, std::vector<typename Problem
     HIP_CHECK(hipMemcpyAsync(bufs.pool.p, nodes.data(), n * sizeof(NodeT),
                              hipMemcpyHostToDevice, stream.s));
   upload_ctl_pair(bufs.ctl.p, ctl, stream.s);
+  (void)hipGetLastError();  // drop a stale launch error of an earlier, unchecked call
   P.enqueue(bufs, bufs.ctl.p, bufs.ctl.p + 1, m, Mi, ps, stream.s);
   HIP_CHECK(hipGetLastError());
   return step_readback(nodes, bufs.pool.p, bufs.ctl.p + 1, capacity, stream.s);
@@ -241,6 +242,7 @@ std::vector<DevpoolSnapshot<typename Problem::Node>> devpool_chain(
   if (n > 0)
     HIP_CHECK(hipMemcpyAsync(pool_d, nodes.data(), n * sizeof(NodeT), hipMemcpyHostToDevice, s));
   upload_ctl_pair(ctl_d, ctl, s);
+  (void)hipGetLastError();  // drop a stale launch error of an earlier, unchecked call
   for (size_t i = 0; i < k; i++) {
     DevCtl* cur = ctl_d + (i & 1);
     DevCtl* next = ctl_d + 1 - (i & 1);

@@ -29,6 +29,7 @@
 #include <type_traits>
 
 #include "gpu_api.hpp"
+#include "nq_finish.hpp"
 
 namespace gats {
 
@@ -151,22 +152,6 @@ __device__ inline uint8_t nq_safe(const uint8_t* board, int depth, int q, int g)
     }
   }
   return safe;
-}
-
-// Free-column mask evaluated g times as a LIVE dependency chain (devpool
-// path's g semantics: the per-node safety evaluation is the mask combine +
-// negate, so g repeats exactly that). Each repeat's asm makes `occ` opaque,
-// so the ORs/ANDN must really execute every round; the result is the
-// identity ~(cols|d1|d2) & msk.
-__device__ inline uint32_t nq_free_g(uint32_t cols, uint32_t d1, uint32_t d2, uint32_t msk,
-                                     int g) {
-  uint32_t free = 0, occ = cols | d1 | d2;
-  for (int r = 0; r < g; r++) {
-    asm volatile("" : "+v"(occ));
-    occ |= cols | d1 | d2;  // identity; non-foldable through the barrier
-    free |= ~occ & msk;     // idempotent accumulate keeps every repeat live
-  }
-  return free;
 }
 
 // hostpool mode: one thread per (parent, k), labels out
@@ -665,42 +650,7 @@ __device__ inline unsigned long long block_reduce_u64(unsigned long long v) {
   return wsum[0] + wsum[1] + wsum[2] + wsum[3];
 }
 
-// Register-resident bitmask DFS over the last levels of the N-Queens tree:
-// counts every safe node (tree) and every depth-N placement (sol) below the
-// current state. Equivalent to the reference's decomposition: candidate
-// VALUES are the unused ones (cols mask == the permutation's remaining
-// values) and safety is the two diagonal masks — identical node set, and
-// N-Queens counts are traversal-order independent. Template depth budget B
-// keeps every stack frame in registers (no runtime-indexed arrays).
-// G1=true is the hot path (no g argument threaded through the recursion at
-// all — a runtime g branch per node measured ~30% on N=17); G1=false repeats
-// every node's mask evaluation g times via nq_occ_g.
-template <int B, bool G1>
-__device__ inline void nq_dfs(uint32_t cols, uint32_t d1, uint32_t d2, int placed, int N,
-                              int g, unsigned long long& tree, unsigned long long& sol) {
-  if constexpr (B == 0) {
-    return;
-  } else {
-    const uint32_t msk = (1u << N) - 1u;
-    uint32_t free;
-    if constexpr (G1)
-      free = ~(cols | d1 | d2) & msk;
-    else
-      free = nq_free_g(cols, d1, d2, msk, g);
-    while (free) {
-      const uint32_t bit = free & (0u - free);
-      free ^= bit;
-      tree++;
-      if (placed + 1 == N) {
-        sol++;
-      } else {
-        nq_dfs<B - 1, G1>(cols | bit, ((d1 | bit) << 1) & msk, (d2 | bit) >> 1, placed + 1,
-                          N, g, tree, sol);
-      }
-    }
-  }
-}
-constexpr int NQ_FINISH_MAX = 8;
+constexpr int NQ_FINISH_MAX = NQ_FLAT_LEVELS_DEV;  // deepest subtree finished in-kernel
 
 // popBackBulk chunk, re-derived identically by every kernel of an iteration
 // (pure function of ctl->size, which only K2 of the previous iteration wrote).
@@ -713,12 +663,18 @@ __device__ inline unsigned long long derive_chunk(const DevCtl* ctl, unsigned lo
 }
 
 // K1 for N-Queens: evaluate + compact children into the block's childbuf slab.
-// Children within `finish` levels of the bottom are counted in-thread by the
-// bitmask DFS (nq_dfs) instead of being pushed: the deepest levels dominate
-// the tree, so the pool machinery only carries the shallow part.
+// Children within `finish` levels of the bottom are counted in-kernel by the
+// flat bitmask DFS (nq_finish.hpp) instead of being pushed: the deepest levels
+// dominate the tree, so the pool machinery only carries the shallow part.
 // A phase-A pass computes each PARENT's (cols, d1, d2) diagonal masks once
 // (one thread per staged parent), so a child's safety test and the finisher's
 // starting masks are O(1) instead of an O(depth) walk per child.
+// Phase B classifies the block's 1024 child slots; the slots that start a
+// subtree walk (a safe child with 0 < rem <= finish) become jobs, compacted
+// in slot order into an LDS queue (wave ballots + a 16-entry count table: no
+// atomics, so the order is the same in every run). Phase C drains the queue:
+// thread t walks jobs t, t + 256, ... in ONE loop (nq_flat_run), so a wave's
+// lanes stay busy whatever depth or job each of them is in.
 template <bool G1>
 __global__ void k_nq_x(const DevCtl* ctl, const NQNode* pool, NQNode* childbuf,
                        uint32_t* blockCounts, unsigned long long* blockSols,
@@ -726,6 +682,8 @@ __global__ void k_nq_x(const DevCtl* ctl, const NQNode* pool, NQNode* childbuf,
                        unsigned long long m, unsigned long long M) {
   __shared__ NQNode s[EMIT_TILE / 4 + 2];  // N >= 4 (engine falls back below)
   __shared__ uint32_t pmask[EMIT_TILE / 4 + 2][3];  // per-parent cols/d1/d2
+  __shared__ uint16_t jobq[EMIT_TILE];  // finisher jobs: local parent id * 32 + k
+  __shared__ uint32_t jobcnt[(EMIT_TILE / BLOCK) * (BLOCK / 64)];  // jobs per (j, wave)
   const unsigned long long c = derive_chunk(ctl, m, M);
   // child indices fit u32: the engine enforces M * branching <= 2^31
   const uint32_t total = static_cast<uint32_t>(c * N);
@@ -734,16 +692,16 @@ __global__ void k_nq_x(const DevCtl* ctl, const NQNode* pool, NQNode* childbuf,
   uint32_t cnt = 0;
   unsigned long long sols = 0, extra = 0;
   unsigned int first = 0;
-  uint8_t lab[EMIT_TILE / BLOCK] = {0, 0, 0, 0};
+  uint8_t lab[EMIT_TILE / BLOCK] = {0, 0, 0, 0};  // 1 = pushed child, 2 = finisher job
   uint16_t lpid[EMIT_TILE / BLOCK];
   uint8_t lk[EMIT_TILE / BLOCK];
   if (c0 < total) {
+    const uint32_t msk = (1u << N) - 1u;
     uint32_t c1 = c0 + EMIT_TILE;
     if (c1 > total) c1 = total;
     first = stage_range(parents, c0, c1, N, s);
     __syncthreads();
     {  // phase A: one thread per staged parent
-      const uint32_t msk = (1u << N) - 1u;
       const int nblk = static_cast<int>((c1 - 1) / N - first + 1);
       for (int pi = threadIdx.x; pi < nblk; pi += blockDim.x) {
         const NQNode& p = s[pi];
@@ -762,7 +720,7 @@ __global__ void k_nq_x(const DevCtl* ctl, const NQNode* pool, NQNode* childbuf,
     }
     __syncthreads();
 #pragma unroll
-    for (int j = 0; j < EMIT_TILE / BLOCK; j++) {
+    for (int j = 0; j < EMIT_TILE / BLOCK; j++) {  // phase B: classify the child slots
       const uint32_t t = c0 + j * BLOCK + threadIdx.x;
       if (t < total) {
         const uint32_t pid = t / static_cast<uint32_t>(N);
@@ -774,24 +732,19 @@ __global__ void k_nq_x(const DevCtl* ctl, const NQNode* pool, NQNode* childbuf,
         if (depth == N) {
           sols += (k == 0);  // leaf parent counted once (nqueens_chpl.chpl:78-80)
         } else if (k >= depth) {
-          const uint32_t cols = pmask[pid - first][0];
-          const uint32_t d1 = pmask[pid - first][1];
-          const uint32_t d2 = pmask[pid - first][2];
+          const uint32_t* pm = pmask[pid - first];
+          const uint32_t occ = pm[0] | pm[1] | pm[2];
           const uint32_t b = 1u << p.board[k];
-          const uint32_t msk = (1u << N) - 1u;
-          const uint32_t freemask =
-              G1 ? (~(cols | d1 | d2) & msk) : nq_free_g(cols, d1, d2, msk, g);
+          const uint32_t freemask = G1 ? (~occ & msk) : nq_free_occ_g(occ, msk, g);
           if (b & freemask) {  // == nq_safe (diagonal masks)
             const int rem = N - (depth + 1);  // levels below the child
             if (rem <= finish) {
               // child + its whole subtree counted here, nothing pushed
               extra += 1;
-              if (rem == 0) {
+              if (rem == 0)
                 sols += 1;
-              } else {
-                nq_dfs<NQ_FINISH_MAX, G1>(cols | b, ((d1 | b) << 1) & msk, (d2 | b) >> 1,
-                                          depth + 1, N, g, extra, sols);
-              }
+              else
+                lab[j] = 2;
             } else {
               lab[j] = 1;
             }
@@ -800,6 +753,51 @@ __global__ void k_nq_x(const DevCtl* ctl, const NQNode* pool, NQNode* childbuf,
         cnt += (lab[j] == 1);
       }
     }
+    // job queue: slot j * 256 + threadIdx.x ranks as (j, wave, lane)
+    const int lane = threadIdx.x & 63;
+    const int wid = threadIdx.x >> 6;
+    uint32_t rank[EMIT_TILE / BLOCK];
+#pragma unroll
+    for (int j = 0; j < EMIT_TILE / BLOCK; j++) {
+      const unsigned long long bal = __ballot(lab[j] == 2);
+      rank[j] = static_cast<uint32_t>(__popcll(bal & ((1ull << lane) - 1ull)));
+      if (lane == 0) jobcnt[j * (BLOCK / 64) + wid] = static_cast<uint32_t>(__popcll(bal));
+    }
+    __syncthreads();
+    uint32_t njobs = 0;
+#pragma unroll
+    for (int i = 0; i < (EMIT_TILE / BLOCK) * (BLOCK / 64); i++) {
+      if (i % (BLOCK / 64) == wid) rank[i / (BLOCK / 64)] += njobs;
+      njobs += jobcnt[i];
+    }
+#pragma unroll
+    for (int j = 0; j < EMIT_TILE / BLOCK; j++)
+      if (lab[j] == 2) jobq[rank[j]] = static_cast<uint16_t>(lpid[j] * 32u + lk[j]);
+    __syncthreads();
+    // phase C: one flat loop per lane over its share of the queue
+    static_assert(MAX_JOBS <= 32 && (EMIT_TILE / 4 + 2) * 32 <= 65536, "jobq entry is 16-bit");
+    NqFlat<NQ_FLAT_LEVELS_DEV> st;
+    st.tree = 0;
+    st.sol = 0;
+    uint32_t q = threadIdx.x;
+    nq_flat_run<NQ_FLAT_LEVELS_DEV, G1>(
+        st,
+        [&](NqFlat<NQ_FLAT_LEVELS_DEV>& w) {
+          if (q >= njobs) return false;
+          const uint32_t e = jobq[q];
+          q += BLOCK;
+          const uint32_t pi = e >> 5;
+          const NQNode& p = s[pi];
+          const uint32_t b = 1u << p.board[e & 31u];
+          // the child's masks, seen from the row below it (as phase A steps them)
+          w.template load<G1>(pmask[pi][0] | b, ((pmask[pi][1] | b) << 1) & msk,
+                              (pmask[pi][2] | b) >> 1, p.depth + 1, N, msk, g);
+          return true;
+        },
+        msk, g);
+    // 32-bit per-lane counters: at most 4 jobs of <= 109,600 nodes each
+    extra += st.tree;
+    sols += st.sol;
   }
   uint32_t totC;
   const uint32_t pre = block_excl_scan(cnt, totC);

@@ -1,0 +1,169 @@
+// Flat (single-loop, stackless) bitmask DFS over the last levels of the
+// N-Queens tree. Shared by the k_nq_x finisher (device) and by the CPU entry
+// point nq_finish_count_cpu, so the loop that runs on the GPU is the loop the
+// CPU tests walk.
+//
+// A job is the state below one safe child: (cols, d1, d2) are the occupied
+// column / diagonal masks seen from row `row` (the first empty row), exactly
+// what the recursive finisher used to receive. The walk counts every safe
+// node below the job (tree) and every placement that fills row N-1 (sol).
+//
+// State, all in scalars (nothing is indexed at run time, so nothing spills):
+//   h      rows below the current row (N - 1 - row); the bottom row is h == 0
+//   cols   occupied columns
+//   D1     diagonal that moves one column up per row, as seen from the current
+//          row: bit c set = column c attacked. Stepped `(D1 | bit) << 1` on the
+//          way down and NEVER masked, so `D1 >> 1` on the way up restores it.
+//   D2     diagonal that moves one column down per row, kept G guard bits to
+//          the left (column c is bit c + G): stepped `(D2 | bit << G) >> 1`,
+//          so the bits that leave the board stay in the word and
+//          `D2 << 1` restores it.
+//          -> free squares of the current row: ~(cols | D1 | D2 >> G) & msk
+//   stack  the columns chosen below the job's root, one 5-bit field per level,
+//          newest lowest, under a sentinel 1 bit; stack == 1 means "at the
+//          job's root", stack == 0 "no job"
+//   cand   candidates of the current row that are still to be taken
+// The bottom row is never descended into (its candidates are counted with one
+// popcount from the row above), so a walk of LEVELS rows descends at most
+// G = LEVELS - 2 times: with N <= 20 both diagonals stay below bit N + G, i.e.
+// inside 32 bits up to LEVELS = 12, and the stack needs 5 G + 1 bits: 31 for
+// LEVELS = 8 (u32, the kernel's instantiation), 51 for LEVELS = 12 (u64, CPU
+// only).
+//
+// One step is "pop if the row is exhausted, then take the next candidate if
+// there is one": lanes of a wave that sit at different depths, or in different
+// jobs, execute the same instructions, and no shift amount depends on the
+// depth. Backtracking keeps no per-level candidate set; it clears the popped
+// column's three bits, re-derives the free mask of that row and drops the
+// candidates up to and including that column.
+#pragma once
+
+#include <cstdint>
+#include <type_traits>
+
+#if defined(__HIPCC__)
+#define NQ_HD __host__ __device__
+#else
+#define NQ_HD
+#endif
+
+namespace gats {
+
+// Free-column mask evaluated g times as a LIVE dependency chain (devpool
+// path's g semantics: the per-node safety evaluation is the mask combine +
+// negate, so g repeats exactly that). Each repeat's asm makes `occ` opaque,
+// so the OR/ANDN must really execute every round; the result is the identity
+// ~occ & msk.
+NQ_HD inline uint32_t nq_free_occ_g(uint32_t occ0, uint32_t msk, int g) {
+  uint32_t free = 0, occ = occ0;
+  for (int r = 0; r < g; r++) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm volatile("" : "+v"(occ));
+#else
+    asm volatile("" : "+r"(occ));
+#endif
+    occ |= occ0;         // identity; non-foldable through the barrier
+    free |= ~occ & msk;  // idempotent accumulate keeps every repeat live
+  }
+  return free;
+}
+
+inline constexpr int NQ_FLAT_LEVELS_DEV = 8;   // == the kernel's finisher depth limit
+inline constexpr int NQ_FLAT_LEVELS_MAX = 12;  // widest walk the 32-bit diagonals hold
+
+template <int LEVELS>
+struct NqFlat {
+  static_assert(LEVELS >= 1 && LEVELS <= NQ_FLAT_LEVELS_MAX, "diagonal masks are 32-bit");
+  static constexpr int G = LEVELS >= 2 ? LEVELS - 2 : 0;
+  using Stack = typename std::conditional<(5 * G + 1 <= 32), uint32_t, uint64_t>::type;
+  uint32_t cols, D1, D2, cand;
+  Stack stack;
+  int h;
+  // subtree counters; 32 bits hold them: a job with r rows left has at most r
+  // free columns, so at most sum_i r!/(r-i)! nodes (109,600 for r = 8,
+  // 1.3e9 for r = 12)
+  uint32_t tree, sol;
+
+  NQ_HD uint32_t occupied() const { return cols | D1 | (D2 >> G); }
+
+  // Start the walk below (cols, d1, d2) at `row`; needs 1 <= N - row <= LEVELS.
+  // G1 == false evaluates the root's free mask g times (its first evaluation).
+  template <bool G1>
+  NQ_HD void load(uint32_t c, uint32_t d1, uint32_t d2, int row, int N, uint32_t msk, int g) {
+    h = N - 1 - row;
+    cols = c;
+    D1 = d1;
+    D2 = d2 << G;
+    stack = 1;
+    const uint32_t occ = occupied();
+    cand = G1 ? (~occ & msk) : nq_free_occ_g(occ, msk, g);
+    if (h == 0) {  // the job's root is the bottom row: every candidate is a solution
+      const uint32_t n = static_cast<uint32_t>(__builtin_popcount(cand));
+      tree += n;
+      sol += n;
+      cand = 0;
+    }
+  }
+
+  // Backtrack one level (stack > 1): re-derive the row's remaining candidates.
+  NQ_HD void pop(uint32_t msk) {
+    const int c = static_cast<int>(stack & 31u);
+    stack >>= 5;
+    const uint32_t bit = 1u << c;
+    h++;
+    cols ^= bit;
+    D1 = (D1 >> 1) ^ bit;
+    D2 = (D2 << 1) ^ (bit << G);
+    cand = ~occupied() & msk & (~1u << c);
+  }
+
+  // Take the lowest candidate of the current row (cand != 0, h >= 1): count
+  // it, count its children with a popcount when they are the bottom row, and
+  // descend only when it has children in an inner row. (`bit` is free, so it
+  // is in none of the three masks and + sets it like | would.)
+  template <bool G1>
+  NQ_HD void take(uint32_t msk, int g) {
+    const uint32_t bit = cand & (0u - cand);
+    cand ^= bit;
+    tree++;
+    const uint32_t nc = cols + bit;
+    const uint32_t n1 = (D1 + bit) << 1;
+    const uint32_t n2 = (D2 + (bit << G)) >> 1;
+    const uint32_t occ = nc | n1 | (n2 >> G);
+    const uint32_t nf = G1 ? (~occ & msk) : nq_free_occ_g(occ, msk, g);
+    if (h == 1) {
+      const uint32_t n = static_cast<uint32_t>(__builtin_popcount(nf));
+      tree += n;
+      sol += n;
+    } else if (nf) {
+      cols = nc;
+      D1 = n1;
+      D2 = n2;
+      stack = (stack << 5) | static_cast<Stack>(__builtin_ctz(bit));
+      h--;
+      cand = nf;
+    }
+  }
+};
+
+// Walk every job `next` hands out, one after the other, in ONE loop: when a
+// subtree is exhausted the same loop iteration loads the next job.
+// next(st) loads a job into st (st.load<G1>(...)) and returns true, or returns
+// false when there is none left.
+template <int LEVELS, bool G1, class Next>
+NQ_HD inline void nq_flat_run(NqFlat<LEVELS>& st, Next&& next, uint32_t msk, int g) {
+  st.cand = 0;
+  st.stack = 0;
+  for (;;) {
+    if (st.cand == 0) {
+      if (st.stack <= 1) {
+        if (!next(st)) break;
+      } else {
+        st.pop(msk);
+      }
+    }
+    if (st.cand) st.template take<G1>(msk, g);
+  }
+}
+
+}  // namespace gats
