@@ -1550,76 +1550,117 @@ __global__ void k_presum(const uint32_t* blockCounts, uint32_t* groupSums, int G
   if (threadIdx.x == 0) groupSums[blockIdx.x] = tot;
 }
 
-// K2+K3 merged ("gather2"): every block derives its own pool offset by
-// summing the counts of the blocks before it (G ~ 1000 u32 loads through L2,
-// done in parallel across blocks — cheaper than serializing on the
-// single-block scan kernel), copies its children, and the LAST block writes
-// the next iteration's control block. Control blocks alternate per iteration
-// (parity) so readers of iteration i never race the writer: expand(i) and
-// gather2(i) read ctl_cur, gather2's last block writes ctl_next, and the
-// kernel boundary publishes it for iteration i+1 (placement-independent).
-template <class NodeT>
+// K2+K3 merged ("gather2"), one RUN of R consecutive count entries per block.
+// Every wave of the block loads the run's R counts into its lanes [0, R); a
+// run that carries no children returns there, before any walk or barrier
+// (most runs do: slabs of parents whose children all went to the in-kernel
+// finisher, and the grid's tail beyond the live chunk). The others derive the
+// run's pool offset once — whole-group sums before the run's group plus the
+// counts of its group before its first entry (R divides 256, so a run never
+// straddles a k_presum group); without groupSums a linear walk over the
+// entries before it — and the in-run offsets by a wave scan of the R counts.
+// Each wave does this redundantly (the loads hit L2), so the copy needs no
+// LDS and no barrier: small slabs go one per wave, a slab above
+// GATHER_WAVE_WORDS is copied by the whole block; destinations are disjoint.
+// The LAST block alone sums the sol / extra counts and writes the next
+// iteration's control block. Control blocks alternate per iteration (parity)
+// so readers of iteration i never race the writer: expand(i) and gather2(i)
+// read ctl_cur, gather2's last block writes ctl_next, and the kernel boundary
+// publishes it for iteration i+1 (placement-independent). Count entries at
+// index >= G are never read: the buffers hold stale counts of wider
+// iterations there.
+constexpr int GATHER_WAVE_WORDS = 256;  // largest slab (8-byte words) left to one wave
+
+template <class NodeT, int R>
 __global__ void k_gather2(const DevCtl* ctl_cur, DevCtl* ctl_next, const uint32_t* blockCounts,
                           const unsigned long long* blockSols,
                           const unsigned long long* blockExtra, const uint32_t* groupSums,
                           const NodeT* childbuf, NodeT* pool, int strideNodes, int G,
                           unsigned long long m, unsigned long long M,
                           unsigned long long capacity) {
+  static_assert(R >= 1 && R <= 64 && (R & (R - 1)) == 0 && BLOCK % R == 0,
+                "a run is a power of two that divides a presum group and fits a wave");
+  static_assert(sizeof(NodeT) % 8 == 0, "nodes are copied as 8-byte words");
+  constexpr int WPN = static_cast<int>(sizeof(NodeT) / 8);
+  const int lane = threadIdx.x & 63;
+  const int wid = threadIdx.x >> 6;
+  const int e0 = static_cast<int>(blockIdx.x) * R;  // first count entry of the run
+  const bool last = (blockIdx.x == gridDim.x - 1);
+
+  // the run's counts, in lanes [0, R) of every wave: the same values in all
+  // four waves, so what follows from them is block-uniform
+  const uint32_t cnt = (lane < R && e0 + lane < G) ? blockCounts[e0 + lane] : 0;
+  if (!last && __ballot(cnt != 0) == 0) return;
+
   const unsigned long long c = derive_chunk(ctl_cur, m, M);
   const unsigned long long base = ctl_cur->size - c;
-  const int b = blockIdx.x;
-  const bool last = (b == G - 1);
+  const bool dead = ctl_cur->overflow != 0;
 
-  // prefix over count entries [0, b) — via whole-group sums when available —
-  // plus full sol/extra sums for the last block
-  uint32_t my_pre = 0;
-  unsigned long long my_sols = 0, my_extra = 0;
+  // prefix over count entries [0, e0), once per run
+  uint32_t pre = 0;
   if (groupSums) {
-    const int gfull = b / BLOCK;  // whole groups strictly before b
-    for (int i = threadIdx.x; i < gfull; i += BLOCK) my_pre += groupSums[i];
-    for (int i = gfull * BLOCK + threadIdx.x; i < b; i += BLOCK) my_pre += blockCounts[i];
-    if (last) {
-      for (int i = threadIdx.x; i < G; i += BLOCK) {
-        my_sols += blockSols[i];
-        if (blockExtra) my_extra += blockExtra[i];
-      }
-    }
+    const int gfull = e0 / BLOCK;  // whole groups strictly before the run
+    for (int i = lane; i < gfull; i += 64) pre += groupSums[i];
+    for (int i = gfull * BLOCK + lane; i < e0; i += 64) pre += blockCounts[i];
   } else {
-    for (int i = threadIdx.x; i < G; i += BLOCK) {
-      if (i < b) my_pre += blockCounts[i];
-      if (last) {
-        my_sols += blockSols[i];
-        if (blockExtra) my_extra += blockExtra[i];
-      }
-    }
+    for (int i = lane; i < e0; i += 64) pre += blockCounts[i];
   }
-  uint32_t pre_tot;
-  block_excl_scan(my_pre, pre_tot);
-  const unsigned long long sol_tot = block_reduce_u64(my_sols);
-  const unsigned long long extra_tot = block_reduce_u64(my_extra);
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) pre += __shfl_xor(pre, d);
 
-  const uint32_t cnt = blockCounts[b];
-  const unsigned long long off = base + pre_tot;
-  const bool over = ctl_cur->overflow || (off + cnt > capacity);
-  if (!over && cnt > 0) {
+  // inclusive scan of the run's counts over lanes [0, R)
+  uint32_t inc = cnt;
+#pragma unroll
+  for (int d = 1; d < R; d <<= 1) {
+    const uint32_t y = __shfl_up(inc, d);
+    if (lane >= d) inc += y;
+  }
+  const uint32_t run_tot = static_cast<uint32_t>(
+      __builtin_amdgcn_readlane(static_cast<int>(inc), R - 1));
+
+  // copy the non-empty slabs, in entry order of the pool
+  bool over = dead;
+  for (int s = 0; s < R; s++) {
+    const uint32_t cs = static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(cnt), s));
+    if (cs == 0) continue;
+    const uint32_t is = static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(inc), s));
+    const unsigned long long off = base + pre + (is - cs);
+    if (dead || off + cs > capacity) {
+      over = true;
+      continue;
+    }
+    const int words = static_cast<int>(cs) * WPN;
+    const bool whole = words > GATHER_WAVE_WORDS;
+    if (!whole && (s & 3) != wid) continue;
     const unsigned long long* src = reinterpret_cast<const unsigned long long*>(
-        childbuf + static_cast<unsigned long long>(b) * strideNodes);
+        childbuf + static_cast<unsigned long long>(e0 + s) * strideNodes);
     unsigned long long* dst = reinterpret_cast<unsigned long long*>(pool + off);
-    const int words = static_cast<int>(cnt) * static_cast<int>(sizeof(NodeT) / 8);
-    for (int i = threadIdx.x; i < words; i += BLOCK) dst[i] = src[i];
+    const int step = whole ? BLOCK : 64;
+    for (int i = whole ? static_cast<int>(threadIdx.x) : lane; i < words; i += step)
+      dst[i] = src[i];
   }
   if (over && threadIdx.x == 0) ctl_next->overflow = 1;  // sticky; host aborts
-  if (last && threadIdx.x == 0) {
-    const unsigned long long total = pre_tot + cnt;
-    if (!ctl_cur->overflow && off + cnt <= capacity) {
-      ctl_next->size = base + total;
-      ctl_next->tree = ctl_cur->tree + total + extra_tot;
-      ctl_next->sol = ctl_cur->sol + sol_tot;
-      ctl_next->iters = ctl_cur->iters + (c > 0);
-      ctl_next->chunk = c;
-      ctl_next->overflow = ctl_cur->overflow;
+
+  if (last) {  // block-uniform: the barriers below are reached by the whole block
+    unsigned long long my_sols = 0, my_extra = 0;
+    for (int i = threadIdx.x; i < G; i += BLOCK) {
+      my_sols += blockSols[i];
+      if (blockExtra) my_extra += blockExtra[i];
     }
-    ctl_next->best = ctl_cur->best;  // carries expand's atomicMin updates
+    const unsigned long long sol_tot = block_reduce_u64(my_sols);
+    const unsigned long long extra_tot = block_reduce_u64(my_extra);
+    if (threadIdx.x == 0) {
+      const unsigned long long total = static_cast<unsigned long long>(pre) + run_tot;
+      if (!dead && base + total <= capacity) {
+        ctl_next->size = base + total;
+        ctl_next->tree = ctl_cur->tree + total + extra_tot;
+        ctl_next->sol = ctl_cur->sol + sol_tot;
+        ctl_next->iters = ctl_cur->iters + (c > 0);
+        ctl_next->chunk = c;
+        ctl_next->overflow = ctl_cur->overflow;
+      }
+      ctl_next->best = ctl_cur->best;  // carries expand's atomicMin updates
+    }
   }
 }
 
@@ -1772,13 +1813,51 @@ void launch_presum(const uint32_t* bc, uint32_t* groupSums, int G, hipStream_t s
                      groupSums, G);
 }
 
+// Count entries per gather block. One value serves every geometry (BASELINE.md,
+// "Gather by runs"); GATS_GATHER_R = 4 / 8 / 16 / 32 overrides it for sweeps.
+constexpr int GATHER_RUN = 4;
+
+static int gather_run() {
+  static const int r = [] {
+    if (const char* e = std::getenv("GATS_GATHER_R")) {
+      const int v = atoi(e);
+      if (v == 4 || v == 8 || v == 16 || v == 32) return v;
+    }
+    return GATHER_RUN;
+  }();
+  return r;
+}
+
+template <class NodeT>
+static void launch_gather2(const DevCtl* ctl_cur, DevCtl* ctl_next, const uint32_t* bc,
+                           const unsigned long long* bs, const unsigned long long* be,
+                           const uint32_t* groupSums, const NodeT* childbuf, NodeT* pool,
+                           int strideNodes, int G, unsigned long long m, unsigned long long M,
+                           unsigned long long capacity, hipStream_t s) {
+  const int R = gather_run();
+  const dim3 grid((G + R - 1) / R);
+#define GATS_GATHER_CASE(RR)                                                                  \
+  case RR:                                                                                    \
+    hipLaunchKernelGGL((k_gather2<NodeT, RR>), grid, dim3(BLOCK), 0, s, ctl_cur, ctl_next, bc, \
+                       bs, be, groupSums, childbuf, pool, strideNodes, G, m, M, capacity);    \
+    break;
+  switch (R) {
+    GATS_GATHER_CASE(4)
+    GATS_GATHER_CASE(8)
+    GATS_GATHER_CASE(32)
+    default:
+      GATS_GATHER_CASE(16)
+  }
+#undef GATS_GATHER_CASE
+}
+
 void launch_gather2_nq(const DevCtl* ctl_cur, DevCtl* ctl_next, const uint32_t* bc,
                        const unsigned long long* bs, const unsigned long long* be,
                        const uint32_t* groupSums, const NQNode* childbuf, NQNode* pool,
                        int strideNodes, int G, unsigned long long m, unsigned long long M,
                        unsigned long long capacity, hipStream_t s) {
-  hipLaunchKernelGGL(k_gather2<NQNode>, dim3(G), dim3(BLOCK), 0, s, ctl_cur, ctl_next, bc,
-                     bs, be, groupSums, childbuf, pool, strideNodes, G, m, M, capacity);
+  launch_gather2<NQNode>(ctl_cur, ctl_next, bc, bs, be, groupSums, childbuf, pool, strideNodes,
+                         G, m, M, capacity, s);
 }
 
 void launch_gather2_pfsp(const DevCtl* ctl_cur, DevCtl* ctl_next, const uint32_t* bc,
@@ -1786,9 +1865,8 @@ void launch_gather2_pfsp(const DevCtl* ctl_cur, DevCtl* ctl_next, const uint32_t
                          const PFSPNode* childbuf, PFSPNode* pool, int strideNodes, int G,
                          unsigned long long m, unsigned long long M,
                          unsigned long long capacity, hipStream_t s) {
-  hipLaunchKernelGGL(k_gather2<PFSPNode>, dim3(G), dim3(BLOCK), 0, s, ctl_cur, ctl_next, bc,
-                     bs, static_cast<const unsigned long long*>(nullptr), groupSums,
-                     childbuf, pool, strideNodes, G, m, M, capacity);
+  launch_gather2<PFSPNode>(ctl_cur, ctl_next, bc, bs, nullptr, groupSums, childbuf, pool,
+                           strideNodes, G, m, M, capacity, s);
 }
 
 }  // namespace gats
