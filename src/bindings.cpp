@@ -413,6 +413,94 @@ py::list pfsp_devpool_chain_py(const py::bytes& nodes, int inst, const std::stri
   return chain_to_list(snaps);
 }
 
+// One slice through the real slice thread and loop driver (driver-level
+// tests): totals, leftovers, diag counters and the driver's trace as a list of
+// dicts ("kind" is "run", "batch" or "spill"; engine_gpu.hpp has the fields).
+template <class NodeT>
+py::dict loop_out_to_dict(const DevpoolLoopOut<NodeT>& o) {
+  py::dict d;
+  d["tree"] = o.tree;
+  d["sol"] = o.sol;
+  d["best"] = o.best;
+  d["iters"] = o.iters;
+  d["leftover"] = nodes_to_bytes(o.leftover.data(), o.leftover.size());
+  d["diag"] = result_to_dict(o.diag)["diag"];
+  py::list trace;
+  for (const DevLoopRec& r : o.trace.recs) {
+    py::dict t;
+    const py::bytes nodes(reinterpret_cast<const char*>(r.nodes.data()), r.nodes.size());
+    if (r.kind == DevLoopRec::RUN) {
+      t["kind"] = "run";
+      t["from_spill"] = r.from_spill;
+      t["init_size"] = r.size_before;
+      t["leftover"] = r.size_after;
+    } else if (r.kind == DevLoopRec::SPILL) {
+      t["kind"] = "spill";
+      t["size_before"] = r.size_before;
+      t["size_after"] = r.size_after;
+      t["moved"] = nodes;
+    } else {
+      t["kind"] = "batch";
+      t["b"] = r.b;
+      t["parity"] = r.parity;
+      t["graph"] = r.graph;
+      t["captured"] = r.captured;
+      t["size_before"] = r.size_before;
+      t["ctl"] = step_ctl_to_dict(r.ctl);
+      t["pool"] = nodes;
+    }
+    trace.append(t);
+  }
+  d["trace"] = trace;
+  return d;
+}
+
+unsigned long long loop_arg(long long v, const char* name) {
+  if (v < 0) throw std::invalid_argument(std::string(name) + " must be >= 0");
+  return static_cast<unsigned long long>(v);
+}
+
+py::dict nq_devpool_loop_py(const py::bytes& nodes, int N, int g, int finish, long long m,
+                            long long chunk, long long capacity, bool graph,
+                            long long max_batches, int device) {
+  auto v = nodes_from_bytes<NQNode>(nodes);
+  const unsigned long long mv = loop_arg(m, "m"), cv = loop_arg(chunk, "chunk"),
+                           cap = loop_arg(capacity, "capacity");
+  validate_devpool_loop(v.size(), cv, cap, max_batches);
+  DevpoolLoopOut<NQNode> o;
+  {
+    py::gil_scoped_release rel;
+    o = nq_devpool_loop(v, N, g, finish, mv, cv, cap, graph, static_cast<int>(max_batches),
+                        device);
+  }
+  return loop_out_to_dict(o);
+}
+
+py::dict pfsp_devpool_loop_py(const py::bytes& nodes, int inst, const std::string& lb, int best,
+                              long long m, long long chunk, long long capacity, bool graph,
+                              long long max_batches, const std::string& br,
+                              const py::object& lower_best_at, int device) {
+  auto v = nodes_from_bytes<PFSPNode>(nodes);
+  const unsigned long long mv = loop_arg(m, "m"), cv = loop_arg(chunk, "chunk"),
+                           cap = loop_arg(capacity, "capacity");
+  validate_devpool_loop(v.size(), cv, cap, max_batches);
+  long long lower_at = -1;
+  int lower_to = 0;
+  if (!lower_best_at.is_none()) {
+    const auto kv = lower_best_at.cast<std::pair<long long, int>>();
+    if (kv.first < 0) throw std::invalid_argument("lower_best_at: batch must be >= 0");
+    lower_at = kv.first;
+    lower_to = kv.second;
+  }
+  DevpoolLoopOut<PFSPNode> o;
+  {
+    py::gil_scoped_release rel;
+    o = pfsp_devpool_loop(v, inst, lb, best, mv, cv, cap, graph, static_cast<int>(max_batches),
+                          br, lower_at, lower_to, device);
+  }
+  return loop_out_to_dict(o);
+}
+
 // Exercises pool push/pop/bulk semantics from C++ (unit-test helper).
 py::dict pool_selftest() {
   py::dict d;
@@ -661,6 +749,15 @@ PYBIND11_MODULE(_core, mod) {
           py::arg("lb"), py::arg("best"), py::arg("windows"), py::arg("m") = 1,
           py::arg("capacity") = py::none(), py::arg("geom") = -1,
           py::arg("presum") = "auto", py::arg("device") = 0, py::arg("br") = "fwd");
+  mod.def("nq_devpool_loop", &nq_devpool_loop_py, py::arg("nodes"), py::arg("N"),
+          py::arg("g") = 1, py::arg("finish") = 8, py::arg("m") = 25, py::arg("chunk") = 256,
+          py::arg("capacity") = 1 << 16, py::arg("graph") = true,
+          py::arg("max_batches") = 0, py::arg("device") = 0);
+  mod.def("pfsp_devpool_loop", &pfsp_devpool_loop_py, py::arg("nodes"), py::arg("inst"),
+          py::arg("lb"), py::arg("best"), py::arg("m") = 25, py::arg("chunk") = 256,
+          py::arg("capacity") = 1 << 16, py::arg("graph") = true,
+          py::arg("max_batches") = 0, py::arg("br") = "fwd",
+          py::arg("lower_best_at") = py::none(), py::arg("device") = 0);
 
   mod.def("pool_selftest", &pool_selftest);
   // pure policy helpers (CPU-unit-testable): kernel geometry selection and

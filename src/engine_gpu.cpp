@@ -388,7 +388,32 @@ struct DevLoopCfg {
   int kernels_per_iter = 2;
   int per = 1;                       // max children per node (grid-bound growth)
   bool allow_graph = true;
+  int max_batches = 0;            // tests: end the loop after this many batches (0 = never)
+  DevLoopTrace* trace = nullptr;  // tests: one record per loop turn (engine_gpu.hpp)
 };
+
+static DevpoolStepCtl step_ctl_of(const DevCtl& c) {
+  return {c.size, c.chunk, c.tree, c.sol, c.iters, c.best, c.overflow};
+}
+
+constexpr unsigned long long LOOP_TRACE_MAX_NODES = 1ull << 22;
+
+// Copy `n` nodes into a trace record: from device memory over the (idle)
+// stream `s`, or from host memory when `on_device` is false.
+static void trace_nodes(DevLoopTrace& t, DevLoopRec& rec, const void* src,
+                        unsigned long long n, bool on_device, hipStream_t s) {
+  t.traced_nodes += n;
+  if (t.traced_nodes > LOOP_TRACE_MAX_NODES)
+    throw std::runtime_error("devpool loop trace exceeds 2^22 nodes");
+  rec.nodes.resize(n * t.node_bytes);
+  if (n == 0) return;
+  if (!on_device) {
+    std::memcpy(rec.nodes.data(), src, rec.nodes.size());
+    return;
+  }
+  HIP_CHECK(hipMemcpyAsync(rec.nodes.data(), src, rec.nodes.size(), hipMemcpyDeviceToHost, s));
+  HIP_CHECK(hipStreamSynchronize(s));
+}
 
 template <class EnqueueIter>
 static DevCtl run_devpool_loop(hipStream_t s, DevCtl* ctl_d, const DevLoopCfg& cfg,
@@ -436,8 +461,14 @@ static DevCtl run_devpool_loop(hipStream_t s, DevCtl* ctl_d, const DevLoopCfg& c
           cfg.capacity > last_size ? cfg.capacity - last_size : 0;
       const unsigned long long bmax = room / cfg.growth;
       if (bmax == 0 && spill_hook && last_size >= 4 * cfg.m && batches > 0) {
-        spill_hook(ctl_h.p, ctl_d + par);
+        if (cfg.trace) {
+          cfg.trace->recs.emplace_back();
+          cfg.trace->recs.back().kind = DevLoopRec::SPILL;
+          cfg.trace->recs.back().size_before = last_size;
+        }
+        spill_hook(ctl_h.p, ctl_d + par);  // fills the record's nodes
         last_size = ctl_h.p->size;
+        if (cfg.trace) cfg.trace->recs.back().size_after = last_size;
         continue;
       }
       if (bmax == 0) {
@@ -449,6 +480,8 @@ static DevCtl run_devpool_loop(hipStream_t s, DevCtl* ctl_d, const DevLoopCfg& c
         b = static_cast<int>(bmax);
       }
     }
+    bool captured = false;
+    const int par_in = par;
     if (graph_allowed && batches >= EAGER_BATCHES && exec == nullptr && b == BATCH &&
         par == 0) {
       // one capture at a time: concurrent captures from the slice threads
@@ -473,11 +506,13 @@ static DevCtl run_devpool_loop(hipStream_t s, DevCtl* ctl_d, const DevLoopCfg& c
         // a successfully captured batch was not EXECUTED; replay it below or
         // re-run eagerly — either way the work happens exactly once
         if (exec == nullptr) (void)hipGetLastError();
+        captured = exec != nullptr;
       } else {
         (void)hipGetLastError();
       }
     }
-    if (exec != nullptr && b == BATCH && par == 0) {
+    const bool replay = exec != nullptr && b == BATCH && par == 0;
+    if (replay) {
       HIP_CHECK(hipGraphLaunch(exec, s));  // even count: parity unchanged
     } else {
       unsigned long long bound = last_size ? last_size : 1;
@@ -499,6 +534,23 @@ static DevCtl run_devpool_loop(hipStream_t s, DevCtl* ctl_d, const DevLoopCfg& c
         ctl_h.p->size > last_size + static_cast<unsigned long long>(b) * cfg.growth)
       fprintf(stderr, "DEVPOOL VIOLATION: size %llu -> %llu after %d iters (growth %llu)\n",
               last_size, ctl_h.p->size, b, cfg.growth);
+    if (cfg.trace) {
+      DevLoopTrace& t = *cfg.trace;
+      t.recs.emplace_back();
+      DevLoopRec& rec = t.recs.back();
+      rec.kind = DevLoopRec::BATCH;
+      rec.b = b;
+      rec.parity = par_in;
+      rec.graph = replay;
+      rec.captured = captured;
+      rec.size_before = last_size;
+      rec.ctl = step_ctl_of(*ctl_h.p);
+      if (!ctl_h.p->overflow) {
+        if (ctl_h.p->size > cfg.capacity)
+          throw std::runtime_error("devpool loop: size exceeds capacity");
+        trace_nodes(t, rec, t.pool_d, ctl_h.p->size, /*on_device=*/true, s);
+      }
+    }
     last_size = ctl_h.p->size;
     if (ctl_h.p->overflow) {
       overflow = true;
@@ -525,6 +577,7 @@ static DevCtl run_devpool_loop(hipStream_t s, DevCtl* ctl_d, const DevLoopCfg& c
     }
     if (cfg.stop_size > 0 && ctl_h.p->size >= cfg.stop_size) break;
     if (ctl_h.p->size < cfg.m) break;
+    if (cfg.max_batches > 0 && batches >= cfg.max_batches) break;
   }
   if (exec != nullptr) {
     (void)hipGraphExecDestroy(exec);
@@ -755,6 +808,14 @@ static void carve_back_half(const SliceReadback<NodeT>& rb, std::mutex* dest_mu,
   rb.r.d2h_bytes += half * sizeof(NodeT);
 }
 
+// What the loop-driver test entry points add to a slice thread: the chunk cap
+// taken as given, a batch limit per loop call and the trace sink.
+struct DevpoolThreadTest {
+  unsigned long long chunk = 0;
+  int max_batches = 0;
+  DevLoopTrace* trace = nullptr;
+};
+
 // Queue-driven slice thread: allocates its device buffers once, then keeps
 // claiming frontier slices from the shared index until none remain. Slices
 // are oversubscribed (~4 per thread) so a thread whose slice finishes early
@@ -771,7 +832,8 @@ static SliceOut devpool_thread(const Problem& problem,
                                std::atomic<int>* shared_best, bool allow_graph,
                                SliceShare* share,
                                std::vector<typename Problem::Node>& leftover,
-                               const SliceReadbackFn<typename Problem::Node>& on_readback) {
+                               const SliceReadbackFn<typename Problem::Node>& on_readback,
+                               const DevpoolThreadTest* test = nullptr) {
   using NodeT = typename Problem::Node;
   set_device_cached(device);
   const Problem P = problem.on_device(device);
@@ -779,9 +841,15 @@ static SliceOut devpool_thread(const Problem& problem,
   SliceOut out;
   out.fin.best = best0;
   Result& r = out.diag;
-  const unsigned long long Mc = devpool_chunk_cap(M, P.per, capacity, P.lbg);
+  const unsigned long long Mc =
+      test ? test->chunk : devpool_chunk_cap(M, P.per, capacity, P.lbg);
   const bool presum = devpool_presum_alloc(devpool_grid(Mc, P.per, P.lbg), P.lbg);
   const DevpoolBufs<NodeT> bufs(capacity, Mc, P.per, P.lbg, Problem::needs_be, presum);
+  DevLoopTrace* const trace = test ? test->trace : nullptr;
+  if (trace) {
+    trace->pool_d = bufs.pool.p;
+    trace->node_bytes = sizeof(NodeT);
+  }
   std::vector<NodeT> spilled;  // capacity-pressure spill, re-run after the slice
 
   auto iter = [&](int parity, unsigned long long bound) {
@@ -794,11 +862,17 @@ static SliceOut devpool_thread(const Problem& problem,
   };
   ReadbackHook spill = [&](DevCtl* hc, DevCtl* live) {
     if (hc->size / 2 == 0) return;
+    const size_t before = spilled.size();
     carve_back_half<NodeT>({hc, live, bufs.pool.p, stream.s, r}, nullptr,
                            [&](unsigned long long half) {
                              spilled.resize(spilled.size() + half);
                              return spilled.data() + (spilled.size() - half);
                            });
+    if (trace) {
+      const unsigned long long half = spilled.size() - before;
+      trace_nodes(*trace, trace->recs.back(), spilled.data() + before, half,
+                  /*on_device=*/false, stream.s);
+    }
   };
 
   DevLoopCfg cfg;
@@ -807,8 +881,20 @@ static SliceOut devpool_thread(const Problem& problem,
   cfg.growth = Mc * P.per;  // worst-case children/iter
   cfg.per = P.per;
   cfg.allow_graph = allow_graph;
+  if (test) {
+    cfg.max_batches = test->max_batches;
+    cfg.trace = trace;
+  }
 
-  auto run_pool = [&](unsigned long long init_size, int init_best) {
+  auto run_pool = [&](unsigned long long init_size, int init_best, bool from_spill = false) {
+    size_t run_rec = 0;
+    if (trace) {
+      run_rec = trace->recs.size();
+      trace->recs.emplace_back();
+      trace->recs.back().kind = DevLoopRec::RUN;
+      trace->recs.back().from_spill = from_spill;
+      trace->recs.back().size_before = init_size;
+    }
     DevCtl ctl{};
     ctl.size = init_size;
     // adopt the freshest incumbent before starting
@@ -826,6 +912,7 @@ static SliceOut devpool_thread(const Problem& problem,
     out.fin.sol += fin.sol;
     if (fin.best < out.fin.best) out.fin.best = fin.best;
     r.gpu_iters += fin.iters;
+    if (trace) trace->recs[run_rec].size_after = fin.size;
     if (fin.size > 0) {
       const size_t base = leftover.size();
       leftover.resize(base + fin.size);
@@ -847,7 +934,7 @@ static SliceOut devpool_thread(const Problem& problem,
                                hipMemcpyHostToDevice, stream.s));
       r.h2d++;
       r.h2d_bytes += take * sizeof(NodeT);
-      run_pool(take, out.fin.best);
+      run_pool(take, out.fin.best, /*from_spill=*/true);
     }
   };
 
@@ -1332,6 +1419,91 @@ Result pfsp_gpu_from_pool(const std::vector<PFSPNode>& nodes, int inst,
   const int best = (best0 > 0) ? best0 : I.init_ub;
   return pfsp_gpu_run(I, lb, pool, m, M, device, mode, 0, 0, best, 0.0, capacity,
                       nullptr);
+}
+
+// ---------------------------------------------------------------------------
+// Loop-driver test entry points (declared in engine_gpu.hpp): one slice
+// through the real devpool_thread, traced. Nothing else goes through them.
+// ---------------------------------------------------------------------------
+
+void validate_devpool_loop(size_t n, unsigned long long chunk, unsigned long long capacity,
+                           long long max_batches) {
+  if (capacity < 1 || capacity > LOOP_TRACE_MAX_NODES)
+    throw std::invalid_argument("capacity must be in 1..2^22 nodes");
+  if (chunk > capacity) throw std::invalid_argument("chunk must be <= capacity");
+  if (max_batches < 0 || max_batches > 4096)
+    throw std::invalid_argument("max_batches must be in 0..4096");
+  if (n == 0) throw std::invalid_argument("the pool must hold at least one node");
+}
+
+// Callers validate first: nothing here runs before their checks passed.
+template <class Problem>
+static DevpoolLoopOut<typename Problem::Node> devpool_loop_traced(
+    const Problem& problem, const std::vector<typename Problem::Node>& nodes, int best0,
+    unsigned long long m, unsigned long long chunk, unsigned long long capacity, bool graph,
+    int max_batches, std::atomic<int>* sb, long long lower_at, int lower_to, int device) {
+  using NodeT = typename Problem::Node;
+  DevpoolLoopOut<NodeT> out;
+  DevpoolThreadTest test;
+  test.chunk = chunk;
+  test.max_batches = max_batches;
+  test.trace = &out.trace;
+  const std::vector<std::vector<NodeT>> slices{nodes};
+  std::atomic<int> next_slice{0};
+  long long batch = 0;
+  const SliceReadbackFn<NodeT> lower = [&](const SliceReadback<NodeT>&) {
+    if (sb && batch++ == lower_at) {
+      int cur = sb->load(std::memory_order_relaxed);
+      while (lower_to < cur &&
+             !sb->compare_exchange_weak(cur, lower_to, std::memory_order_relaxed)) {
+      }
+    }
+  };
+  (void)hipGetLastError();  // drop a stale launch error of an earlier, unchecked call
+  const SliceOut so =
+      devpool_thread(problem, slices, next_slice, best0, static_cast<int>(m), /*M=*/0, device,
+                     capacity, sb, graph, /*share=*/nullptr, out.leftover, lower, &test);
+  out.tree = so.fin.tree;
+  out.sol = so.fin.sol;
+  out.iters = so.diag.gpu_iters;
+  out.best = so.fin.best;
+  if (sb) out.best = std::min(out.best, sb->load(std::memory_order_relaxed));
+  out.diag = so.diag;
+  out.trace.pool_d = nullptr;
+  return out;
+}
+
+DevpoolLoopOut<NQNode> nq_devpool_loop(const std::vector<NQNode>& nodes, int N, int g,
+                                       int finish, unsigned long long m,
+                                       unsigned long long chunk, unsigned long long capacity,
+                                       bool graph, int max_batches, int device) {
+  // before any HIP call
+  validate_nq_step(nodes, N, g, finish, m, chunk, capacity, "auto");
+  validate_devpool_loop(nodes.size(), chunk, capacity, max_batches);
+  if (m > (1ull << 30)) throw std::invalid_argument("m must be <= 2^30");
+  return devpool_loop_traced(NqDevProblem(N, g, finish), nodes, /*best0=*/0, m, chunk,
+                             capacity, graph, max_batches, nullptr, -1, 0, device);
+}
+
+DevpoolLoopOut<PFSPNode> pfsp_devpool_loop(const std::vector<PFSPNode>& nodes, int inst,
+                                           const std::string& lb, int best,
+                                           unsigned long long m, unsigned long long chunk,
+                                           unsigned long long capacity, bool graph,
+                                           int max_batches, const std::string& br,
+                                           long long lower_at, int lower_to, int device) {
+  // before any HIP call
+  validate_pfsp_step(nodes, inst, lb, m, chunk, capacity, /*geom=*/-1, "auto", br);
+  validate_devpool_loop(nodes.size(), chunk, capacity, max_batches);
+  if (m > (1ull << 30)) throw std::invalid_argument("m must be <= 2^30");
+  if (best < 1) throw std::invalid_argument("best must be >= 1");
+  if (lower_at < -1) throw std::invalid_argument("lower_best_at: batch must be >= 0");
+  if (lower_at >= 0 && lower_to < 1)
+    throw std::invalid_argument("lower_best_at: value must be >= 1");
+  const PfspInstance& I = pfsp_instance_cached(inst, 1, branching_from_string(br));
+  std::atomic<int> sb{best};
+  return devpool_loop_traced(
+      PfspDevProblem(I, devpool_lbk_geom(lbk_of(lb_from_string(lb)), I.machines)), nodes, best,
+      m, chunk, capacity, graph, max_batches, &sb, lower_at, lower_to, device);
 }
 
 // ---------------------------------------------------------------------------

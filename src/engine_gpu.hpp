@@ -1,5 +1,6 @@
 // Public API of the single-GPU engines (implemented in engine_gpu.cpp; the
-// test-only entry points at the end in engine_testing.cpp).
+// test-only entry points at the end in engine_testing.cpp, except the
+// loop-driver ones, which sit next to the slice thread they run).
 #pragma once
 #include <atomic>
 #include <condition_variable>
@@ -246,6 +247,65 @@ std::vector<DevpoolSnapshot<PFSPNode>> pfsp_devpool_chain(
     unsigned long long m, const std::vector<unsigned long long>& windows,
     unsigned long long capacity, int geom, const std::string& presum, int device,
     const std::string& br = "fwd");
+
+// Loop-driver entry points (driver-level tests; implemented in engine_gpu.cpp
+// next to the code they run): ONE slice goes through the real slice thread —
+// run_pool, the loop driver, the capacity spill, drain_spilled and the
+// leftover copy — with no SliceShare, the chunk cap `chunk` taken as given
+// (no --M floor, no environment variable) and graph replay allowed or not by
+// `graph`. `max_batches` (0 = unlimited) ends every loop call after that many
+// batches; the pool then comes back as leftovers. The driver appends to the
+// trace, in order:
+//   RUN    at every run_pool call: from_spill (started from a drained spill
+//          chunk, not from the slice), size_before = the pool it starts with,
+//          size_after = the leftover count it returned;
+//   BATCH  per readback: b iterations entered on control block `parity`,
+//          graph / captured = replayed / captured in this turn, size_before,
+//          the control block read back, and the first ctl.size pool nodes
+//          copied while the stream is idle (none once overflow is set);
+//   SPILL  per spill: the sizes around it and the nodes moved to the host.
+// The trace copies are not counted in the diag counters. pfsp: `best` is the
+// starting incumbent; lower_at >= 0 lowers the shared incumbent to lower_to
+// from the readback hook of batch lower_at (counted over the whole call), so
+// that the driver's own adoption writes it to the live control block.
+// Everything is validated on the host before the first HIP call (the step
+// entry points' checks, capacity <= 2^22 nodes); the trace itself is capped
+// at 2^22 nodes in total (std::runtime_error beyond).
+struct DevLoopRec {
+  enum Kind { RUN = 0, BATCH = 1, SPILL = 2 };
+  int kind = BATCH;
+  int b = 0, parity = 0;
+  bool graph = false, captured = false, from_spill = false;
+  unsigned long long size_before = 0, size_after = 0;
+  DevpoolStepCtl ctl{};
+  std::vector<unsigned char> nodes;  // BATCH: the pool; SPILL: the moved nodes
+};
+struct DevLoopTrace {
+  std::vector<DevLoopRec> recs;
+  unsigned long long traced_nodes = 0;
+  const void* pool_d = nullptr;  // set by the slice thread
+  size_t node_bytes = 0;
+};
+template <class NodeT>
+struct DevpoolLoopOut {
+  uint64_t tree = 0, sol = 0, iters = 0;
+  int best = 0;
+  std::vector<NodeT> leftover;
+  Result diag;
+  DevLoopTrace trace;
+};
+void validate_devpool_loop(size_t n, unsigned long long chunk, unsigned long long capacity,
+                           long long max_batches);
+DevpoolLoopOut<NQNode> nq_devpool_loop(const std::vector<NQNode>& nodes, int N, int g,
+                                       int finish, unsigned long long m,
+                                       unsigned long long chunk, unsigned long long capacity,
+                                       bool graph, int max_batches, int device);
+DevpoolLoopOut<PFSPNode> pfsp_devpool_loop(const std::vector<PFSPNode>& nodes, int inst,
+                                           const std::string& lb, int best,
+                                           unsigned long long m, unsigned long long chunk,
+                                           unsigned long long capacity, bool graph,
+                                           int max_batches, const std::string& br,
+                                           long long lower_at, int lower_to, int device);
 
 std::vector<uint8_t> nq_gpu_labels(int N, int g, const std::vector<NQNode>& nodes,
                                    int device);

@@ -197,8 +197,9 @@ def test_engines_from_scratch(gpu, inst, engine):
 
 @pytest.mark.parametrize("engine", ["devpool", "hostpool", "rooted"])
 def test_engines_small_chunks(gpu, engine):
-    # M = 64: many iterations per pool — chains, and the captured-graph batches
-    # of the single-slice loop
+    # M = 64 is honoured by hostpool only: in devpool mode --M is a floor under
+    # the 2^19 chunk, so these runs use wide chunks, finish in a handful of
+    # batches and replay no graph (test_gpu_devpool_loop.py does)
     if engine == "rooted":
         r = gpu.pfsp_gpu_rooted(14, "lb1_d", 1, M=64, br="minbranch")
     else:

@@ -304,8 +304,9 @@ def test_engines_match_seq(gpu, inst, br, engine):
 
 @pytest.mark.parametrize("engine", ENGINES)
 def test_engines_small_chunks(gpu, engine):
-    # M = 64: many iterations per pool, and the captured-graph batches of the
-    # single-slice loop
+    # M = 64 is honoured by hostpool only: in devpool mode --M is a floor under
+    # the 2^19 chunk, so these runs use wide chunks, finish in a handful of
+    # batches and replay no graph (test_gpu_devpool_loop.py does)
     r = run_engine(gpu, engine, 14, 1, "minbranch", m=25, M=64)
     assert (r["tree"], r["sol"]) == SEQ[(14, "minbranch")]
 
