@@ -1,0 +1,182 @@
+#!/usr/bin/env python3
+"""CPU model of how k_nq_x's finisher keeps its lanes busy (no GPU needed).
+
+Plays nq_flat_run (src/nq_finish.hpp) literally on sampled N = 17 tiles and
+counts loop iterations per lane. A tile is what one block sees: sibling groups
+of depth-8 parents under random depth-6 prefixes, 60 parents, all their safe
+children as jobs (8 rows left each). A wave is charged 64 x the iterations of
+its longest lane; lane efficiency = iterations that did work / lane slots
+charged. One iteration is charged per job fetch (the iteration that loads a
+job also takes its first candidate, as in the kernel).
+
+Schedules: whole jobs or jobs split 1..3 levels into sub-jobs (the rule of
+nq_split_job: min(S, rem - 1) levels), handed out by static stride
+(t, t + 256, ...) or dynamically (a lane that finishes takes the next queue
+entry), with an optional queue capacity drained in rounds.
+
+What the model leaves out, and what the measurement showed it matters
+(docs/DESIGN.md section 3): the instructions of the fetch path itself. A wave
+executes them whenever ANY of its lanes fetches, so with five sub-jobs per
+lane nearly every iteration of a wave carries a fetch for one or two lanes.
+
+usage: nq_lane_model.py [--tiles 24] [--seed 1] [--N 17]
+"""
+import argparse
+import heapq
+import random
+
+LANES, WAVE = 256, 64
+
+
+def free_of(c, d1, d2, msk):
+    return ~(c | d1 | d2) & msk
+
+
+def down(c, d1, d2, bit, msk):
+    return c | bit, ((d1 | bit) << 1) & msk, (d2 | bit) >> 1
+
+
+def flat_iters(c, d1, d2, row, N):
+    """Iterations nq_flat_run spends on the job, the loading one included."""
+    msk = (1 << N) - 1
+    h = N - 1 - row
+    stack, cand, loaded, it = [], 0, False, 0
+    while True:
+        if cand == 0:
+            if not stack:
+                if loaded:
+                    return it
+                loaded = True
+                cand = free_of(c, d1, d2, msk) if h else 0
+            else:  # pop
+                c, d1, d2, col = stack.pop()
+                h += 1
+                cand = free_of(c, d1, d2, msk) & (~1 << col)
+        if cand:  # take
+            bit = cand & -cand
+            cand ^= bit
+            n = down(c, d1, d2, bit, msk)
+            nf = free_of(*n, msk)
+            if h > 1 and nf:
+                stack.append((c, d1, d2, bit.bit_length() - 1))
+                c, d1, d2 = n
+                h -= 1
+                cand = nf
+        it += 1
+
+
+def split(job, N, S):
+    """Sub-jobs of a job, in queue order."""
+    c, d1, d2, row = job
+    msk = (1 << N) - 1
+    out = [job]
+    for _ in range(max(0, min(S, N - row - 1))):
+        nxt = []
+        for (c, d1, d2, row) in out:
+            f = free_of(c, d1, d2, msk)
+            while f:
+                bit = f & -f
+                f ^= bit
+                nxt.append(down(c, d1, d2, bit, msk) + (row + 1,))
+        out = nxt
+    return out
+
+
+def sample_tile(rng, N, parents=60, prefix_depth=6, parent_depth=8):
+    msk = (1 << N) - 1
+
+    def children(node):
+        c, d1, d2, row = node
+        f = free_of(c, d1, d2, msk)
+        while f:
+            bit = f & -f
+            f ^= bit
+            yield down(c, d1, d2, bit, msk) + (row + 1,)
+
+    tile = []
+    while len(tile) < parents:
+        node = (0, 0, 0, 0)
+        while node and node[3] < prefix_depth:  # a random safe prefix
+            kids = list(children(node))
+            node = rng.choice(kids) if kids else None
+        if node is None:
+            continue
+        level = [node]
+        for _ in range(parent_depth - prefix_depth):
+            level = [k for n in level for k in children(n)]
+        tile += level
+    tile = tile[:parents]
+    return [k for p in tile for k in children(p)]  # the jobs: safe children
+
+
+def waves_cost(finish):
+    return sum(WAVE * max(finish[w:w + WAVE]) for w in range(0, LANES, WAVE))
+
+
+def run_static(lengths):
+    finish = [0] * LANES
+    for q, n in enumerate(lengths):
+        finish[q % LANES] += n
+    return waves_cost(finish)
+
+
+def run_dynamic(lengths):
+    heap = [(0, t) for t in range(LANES)]
+    finish = [0] * LANES
+    for n in lengths:
+        t0, t = heapq.heappop(heap)
+        finish[t] = t0 + n
+        heapq.heappush(heap, (finish[t], t))
+    return waves_cost(finish)
+
+
+def schedule(jobs, N, S, dynamic, qcap=None):
+    """(work, cost, entries) of one tile."""
+    groups = [[flat_iters(*sj, N) for sj in split(j, N, S)] for j in jobs]
+    run = run_dynamic if dynamic else run_static
+    work = sum(map(sum, groups))
+    entries = sum(map(len, groups))
+    if qcap is None:
+        return work, run([n for g in groups for n in g]), entries
+    cost, cur = 0, []
+    for g in groups:  # rounds: the longest run of jobs that fits
+        if cur and len(cur) + len(g) > qcap:
+            cost += run(cur)
+            cur = []
+        cur += g
+    return work, cost + run(cur), entries
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--tiles", type=int, default=24)
+    ap.add_argument("--seed", type=int, default=1)
+    ap.add_argument("--N", type=int, default=17)
+    a = ap.parse_args()
+    rng = random.Random(a.seed)
+    tiles = [sample_tile(rng, a.N) for _ in range(a.tiles)]
+    rows = [("whole jobs, static stride", 0, False, None),
+            ("whole jobs, dynamic", 0, True, None),
+            ("split 1, static stride", 1, False, None),
+            ("split 1, dynamic", 1, True, None),
+            ("split 2, static stride", 2, False, None),
+            ("split 2, dynamic", 2, True, None),
+            ("split 2, dynamic, queue 1024", 2, True, 1024),
+            ("split 2, dynamic, queue 1728", 2, True, 1728),
+            ("split 2, dynamic, queue 2048", 2, True, 2048),
+            ("split 3, dynamic, queue 2048", 3, True, 2048),
+            ("split 3, dynamic, queue 4096", 3, True, 4096)]
+    base = None
+    print(f"N = {a.N}, {a.tiles} tiles, {sum(map(len, tiles)) / a.tiles:.0f} jobs per tile")
+    print(f"{'schedule':34s} {'entries':>8s} {'lane eff.':>9s} {'cost vs today':>13s}")
+    for name, S, dyn, qcap in rows:
+        work = cost = entries = 0
+        for jobs in tiles:
+            w, c, e = schedule(jobs, a.N, S, dyn, qcap)
+            work, cost, entries = work + w, cost + c, entries + e
+        base = base or cost
+        print(f"{name:34s} {entries / a.tiles:8.0f} {work / cost:9.2f} {cost / base:13.2f}")
+
+
+if __name__ == "__main__":
+    main()

@@ -3,6 +3,7 @@
 #include <pybind11/pybind11.h>
 #include <pybind11/stl.h>
 
+#include <array>
 #include <cstring>
 #include <stdexcept>
 
@@ -91,6 +92,84 @@ py::tuple nq_finish_count_cpu(uint32_t cols, uint32_t d1, uint32_t d2, int row, 
   if ((cols | d1 | d2) >> N) throw std::invalid_argument("mask bits at or above column N");
   return rows <= NQ_FLAT_LEVELS_DEV ? nq_finish_count<NQ_FLAT_LEVELS_DEV>(cols, d1, d2, row, N)
                                     : nq_finish_count<NQ_FLAT_LEVELS_MAX>(cols, d1, d2, row, N);
+}
+
+// CPU run of k_nq_x's split finisher over one block's job queue, with the
+// kernel's own functions in sequence: count and rank the sub-jobs, cut the
+// queue into rounds of at most `qcap` entries, write each round's entries and
+// drain them with one flat loop. jobs: (cols, d1, d2, row) states as
+// nq_finish_count_cpu takes them. Returns (tree, sol, entries, rounds).
+template <bool G1>
+py::tuple nq_finish_block(const std::vector<std::array<uint32_t, 4>>& jobs, int N, int g,
+                          int split, uint32_t qcap) {
+  const uint32_t msk = (1u << N) - 1u;
+  const uint32_t njobs = static_cast<uint32_t>(jobs.size());
+  auto levels = [&](uint32_t q) {
+    return nq_split_levels(split, N - static_cast<int>(jobs[q][3]));
+  };
+  std::vector<uint32_t> off(njobs + 1, 0);
+  uint32_t nodes = 0;
+  for (uint32_t q = 0; q < njobs; q++) {
+    const uint32_t n = nq_split_job<G1, false>(jobs[q][0], jobs[q][1], jobs[q][2], levels(q), msk,
+                                               g, nodes, [](uint32_t, uint32_t, uint32_t) {});
+    if (n > qcap)
+      throw std::invalid_argument("qcap " + std::to_string(qcap) + " is below the " +
+                                  std::to_string(n) + " sub-jobs of job " + std::to_string(q));
+    off[q + 1] = off[q] + n;
+  }
+  NqFlat<NQ_FLAT_LEVELS_DEV> st;
+  st.tree = 0;
+  st.sol = 0;
+  std::vector<uint32_t> subq(qcap);
+  uint32_t rounds = 0;
+  for (uint32_t jb = 0; jb < njobs; rounds++) {
+    const uint32_t je = nq_round_end(off.data(), jb, njobs, qcap);
+    const uint32_t nsub = off[je] - off[jb];
+    for (uint32_t q = jb; q < je; q++) {
+      uint32_t w = off[q] - off[jb], unused = 0;
+      nq_split_job<true, true>(jobs[q][0], jobs[q][1], jobs[q][2], levels(q), msk, 1, unused,
+                               [&](uint32_t nc, uint32_t c1, uint32_t c2) {
+                                 subq[w++] = nq_sub_encode(q, nc, c1, c2);
+                               });
+    }
+    uint32_t head = 0;
+    nq_flat_run<NQ_FLAT_LEVELS_DEV, G1>(
+        st,
+        [&](NqFlat<NQ_FLAT_LEVELS_DEV>& w) {
+          if (head >= nsub) return false;
+          const uint32_t e = subq[head++];
+          const auto& j = jobs[nq_sub_ref(e)];
+          nq_sub_load<G1>(w, e, j[0], j[1], j[2], static_cast<int>(j[3]), N, msk, g);
+          return true;
+        },
+        msk, g);
+    jb = je;
+  }
+  return py::make_tuple(static_cast<uint64_t>(nodes) + st.tree, static_cast<uint64_t>(st.sol),
+                        off[njobs], rounds);
+}
+
+py::tuple nq_finish_block_cpu(const std::vector<std::array<uint32_t, 4>>& jobs, int N, int g,
+                              int split, long long qcap) {
+  if (N < 1 || N > MAX_JOBS) throw std::invalid_argument("N must be in 1..20");
+  if (g < 1) throw std::invalid_argument("g must be >= 1");
+  if (split < 0 || split > NQ_SPLIT_MAX) throw std::invalid_argument("split must be in 0..2");
+  if (qcap < 1 || qcap > (1 << 20)) throw std::invalid_argument("qcap must be in 1..2^20");
+  if (jobs.size() > 1024) throw std::invalid_argument("a block holds at most 1024 jobs");
+  for (const auto& j : jobs) {
+    const int rows = N - static_cast<int>(j[3]);
+    if (rows < 1 || rows > NQ_FLAT_LEVELS_DEV)
+      throw std::invalid_argument("every job needs 1..8 empty rows");
+    if ((j[0] | j[1] | j[2]) >> N) throw std::invalid_argument("mask bits at or above column N");
+  }
+  return g == 1 ? nq_finish_block<true>(jobs, N, g, split, static_cast<uint32_t>(qcap))
+                : nq_finish_block<false>(jobs, N, g, split, static_cast<uint32_t>(qcap));
+}
+
+// The sub-job queue entry codec, for tests: encode, and decode to
+// (ref, ncols, c1, c2).
+py::tuple nq_sub_decode_py(uint32_t e) {
+  return py::make_tuple(nq_sub_ref(e), nq_sub_ncols(e), nq_sub_c1(e), nq_sub_c2(e));
 }
 
 template <typename NodeT>
@@ -328,7 +407,7 @@ py::dict step_ctl_to_dict(const DevpoolStepCtl& c) {
 
 py::tuple nq_devpool_step_py(const py::bytes& nodes, int N, int g, int finish, long long m,
                              const py::object& M, const py::object& capacity,
-                             const std::string& presum, int device) {
+                             const std::string& presum, int device, int split) {
   auto v = nodes_from_bytes<NQNode>(nodes);
   if (m < 0) throw std::invalid_argument("m must be >= 1");
   const unsigned long long Mv = step_arg(M, v.empty() ? 1 : v.size(), "M");
@@ -337,7 +416,7 @@ py::tuple nq_devpool_step_py(const py::bytes& nodes, int N, int g, int finish, l
   {
     py::gil_scoped_release rel;
     c = nq_devpool_step(v, N, g, finish, static_cast<unsigned long long>(m), Mv, cap, presum,
-                        device);
+                        device, split);
   }
   return py::make_tuple(nodes_to_bytes(v.data(), v.size()), step_ctl_to_dict(c));
 }
@@ -382,7 +461,7 @@ py::list chain_to_list(const std::vector<DevpoolSnapshot<NodeT>>& snaps) {
 
 py::list nq_devpool_chain_py(const py::bytes& nodes, int N, const std::vector<long long>& windows,
                              int g, int finish, long long m, const py::object& capacity,
-                             const std::string& presum, int device) {
+                             const std::string& presum, int device, int split) {
   auto v = nodes_from_bytes<NQNode>(nodes);
   if (m < 0) throw std::invalid_argument("m must be >= 1");
   const auto w = chain_windows(windows);
@@ -391,7 +470,7 @@ py::list nq_devpool_chain_py(const py::bytes& nodes, int N, const std::vector<lo
   {
     py::gil_scoped_release rel;
     snaps = nq_devpool_chain(v, N, g, finish, static_cast<unsigned long long>(m), w, cap,
-                             presum, device);
+                             presum, device, split);
   }
   return chain_to_list(snaps);
 }
@@ -697,6 +776,15 @@ PYBIND11_MODULE(_core, mod) {
   mod.def("nq_cpu_labels", &nq_cpu_labels);
   mod.def("nq_finish_count_cpu", &nq_finish_count_cpu, py::arg("cols"), py::arg("d1"),
           py::arg("d2"), py::arg("row"), py::arg("N"));
+  mod.def("nq_finish_block_cpu", &nq_finish_block_cpu, py::arg("jobs"), py::arg("N"),
+          py::arg("g") = 1, py::arg("split") = NQ_SPLIT_DEFAULT,
+          py::arg("qcap") = NQ_SPLIT_QCAP);
+  mod.def("nq_sub_encode", &nq_sub_encode, py::arg("ref"), py::arg("ncols"), py::arg("c1"),
+          py::arg("c2"));
+  mod.def("nq_sub_decode", &nq_sub_decode_py, py::arg("entry"));
+  mod.def("nq_split_default", &nq_split_default);
+  mod.attr("NQ_SPLIT_QCAP") = NQ_SPLIT_QCAP;
+  mod.attr("NQ_SPLIT_MAX") = NQ_SPLIT_MAX;
   mod.def("pfsp_cpu_bounds", &pfsp_cpu_bounds);
   mod.def("pfsp_cpu_bounds_bi", &pfsp_cpu_bounds_bi, py::arg("inst"), py::arg("nodes"));
   mod.def("pfsp_gpu_bounds_bi",
@@ -736,7 +824,7 @@ PYBIND11_MODULE(_core, mod) {
   mod.def("nq_devpool_step", &nq_devpool_step_py, py::arg("nodes"), py::arg("N"),
           py::arg("g") = 1, py::arg("finish") = 8, py::arg("m") = 1,
           py::arg("M") = py::none(), py::arg("capacity") = py::none(),
-          py::arg("presum") = "auto", py::arg("device") = 0);
+          py::arg("presum") = "auto", py::arg("device") = 0, py::arg("split") = -1);
   mod.def("pfsp_devpool_step", &pfsp_devpool_step_py, py::arg("nodes"), py::arg("inst"),
           py::arg("lb"), py::arg("best"), py::arg("m") = 1, py::arg("M") = py::none(),
           py::arg("capacity") = py::none(), py::arg("geom") = -1,
@@ -744,7 +832,7 @@ PYBIND11_MODULE(_core, mod) {
   mod.def("nq_devpool_chain", &nq_devpool_chain_py, py::arg("nodes"), py::arg("N"),
           py::arg("windows"), py::arg("g") = 1, py::arg("finish") = 8, py::arg("m") = 1,
           py::arg("capacity") = py::none(), py::arg("presum") = "auto",
-          py::arg("device") = 0);
+          py::arg("device") = 0, py::arg("split") = -1);
   mod.def("pfsp_devpool_chain", &pfsp_devpool_chain_py, py::arg("nodes"), py::arg("inst"),
           py::arg("lb"), py::arg("best"), py::arg("windows"), py::arg("m") = 1,
           py::arg("capacity") = py::none(), py::arg("geom") = -1,

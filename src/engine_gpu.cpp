@@ -35,6 +35,7 @@
 #include "engine_gpu.hpp"
 #include "engine_internal.hpp"
 #include "gpu_api.hpp"
+#include "nq_finish.hpp"
 #include "search_host.hpp"
 #include "taillard.hpp"
 
@@ -1062,6 +1063,18 @@ static int nq_finish_depth() {
   if (const char* e = std::getenv("GATS_NQ_FINISH")) finish = atoi(e);
   if (finish > 8) finish = 8;
   return finish;
+}
+
+// GATS_NQ_SPLIT: levels (0..2) k_nq_x splits every finisher job into sub-jobs
+// before the lanes draw them from the block's queue; 0 is the whole-job,
+// static-stride finisher. Read once.
+int nq_split_default() {
+  static const int split = [] {
+    int v = NQ_SPLIT_DEFAULT;
+    if (const char* e = std::getenv("GATS_NQ_SPLIT")) v = atoi(e);
+    return v < 0 ? 0 : v > NQ_SPLIT_MAX ? NQ_SPLIT_MAX : v;
+  }();
+  return split;
 }
 
 DevpoolMultiOut nq_devpool_multi(Pool<NQNode>& pool, int N, int g, int m, int M,

@@ -206,10 +206,12 @@ void validate_pfsp_step(const std::vector<PFSPNode>& nodes, int inst, const std:
                         unsigned long long m, unsigned long long M,
                         unsigned long long capacity, int geom, const std::string& presum,
                         const std::string& br = "fwd");
+// split: levels the finisher jobs are split (0..2), < 0 = the engine's default
+int nq_split_default();
 DevpoolStepCtl nq_devpool_step(std::vector<NQNode>& nodes, int N, int g, int finish,
                                unsigned long long m, unsigned long long M,
                                unsigned long long capacity, const std::string& presum,
-                               int device);
+                               int device, int split = -1);
 DevpoolStepCtl pfsp_devpool_step(std::vector<PFSPNode>& nodes, int inst, const std::string& lb,
                                  int best, unsigned long long m, unsigned long long M,
                                  unsigned long long capacity, int geom,
@@ -241,7 +243,7 @@ struct DevpoolSnapshot {
 std::vector<DevpoolSnapshot<NQNode>> nq_devpool_chain(
     const std::vector<NQNode>& nodes, int N, int g, int finish, unsigned long long m,
     const std::vector<unsigned long long>& windows, unsigned long long capacity,
-    const std::string& presum, int device);
+    const std::string& presum, int device, int split = -1);
 std::vector<DevpoolSnapshot<PFSPNode>> pfsp_devpool_chain(
     const std::vector<PFSPNode>& nodes, int inst, const std::string& lb, int best,
     unsigned long long m, const std::vector<unsigned long long>& windows,

@@ -13,6 +13,7 @@
 #include "engine_gpu.hpp"
 #include "engine_internal.hpp"
 #include "gpu_api.hpp"
+#include "nq_finish.hpp"
 #include "search_host.hpp"
 #include "taillard.hpp"
 
@@ -170,9 +171,10 @@ DevpoolStepCtl devpool_step(const Problem& problem, std::vector<typename Problem
 DevpoolStepCtl nq_devpool_step(std::vector<NQNode>& nodes, int N, int g, int finish,
                                unsigned long long m, unsigned long long M,
                                unsigned long long capacity, const std::string& presum,
-                               int device) {
+                               int device, int split) {
   validate_nq_step(nodes, N, g, finish, m, M, capacity, presum);  // before any HIP call
-  return devpool_step(NqDevProblem(N, g, finish), nodes, /*best=*/0, m, M, capacity,
+  if (split > NQ_SPLIT_MAX) throw std::invalid_argument("split must be in 0..2, or < 0");
+  return devpool_step(NqDevProblem(N, g, finish, split), nodes, /*best=*/0, m, M, capacity,
                       presum_mode(presum), device);
 }
 
@@ -295,10 +297,11 @@ std::vector<DevpoolSnapshot<typename Problem::Node>> devpool_chain(
 std::vector<DevpoolSnapshot<NQNode>> nq_devpool_chain(
     const std::vector<NQNode>& nodes, int N, int g, int finish, unsigned long long m,
     const std::vector<unsigned long long>& windows, unsigned long long capacity,
-    const std::string& presum, int device) {
+    const std::string& presum, int device, int split) {
   validate_nq_step(nodes, N, g, finish, m, 1, capacity, presum);  // before any HIP call
+  if (split > NQ_SPLIT_MAX) throw std::invalid_argument("split must be in 0..2, or < 0");
   validate_chain_windows(windows, N, capacity);
-  return devpool_chain(NqDevProblem(N, g, finish), nodes, /*best=*/0, m, windows, capacity,
+  return devpool_chain(NqDevProblem(N, g, finish, split), nodes, /*best=*/0, m, windows, capacity,
                        presum_mode(presum), device);
 }
 

@@ -672,10 +672,15 @@ __device__ inline unsigned long long derive_chunk(const DevCtl* ctl, unsigned lo
 // Phase B classifies the block's 1024 child slots; the slots that start a
 // subtree walk (a safe child with 0 < rem <= finish) become jobs, compacted
 // in slot order into an LDS queue (wave ballots + a 16-entry count table: no
-// atomics, so the order is the same in every run). Phase C drains the queue:
-// thread t walks jobs t, t + 256, ... in ONE loop (nq_flat_run), so a wave's
-// lanes stay busy whatever depth or job each of them is in.
-template <bool G1>
+// atomics, so the order is the same in every run). Phase C drains the queue
+// in ONE loop per lane (nq_flat_run), so a wave's lanes stay busy whatever
+// depth or job each of them is in. SPLIT == 0: thread t walks jobs t, t + 256,
+// ... SPLIT == 1 / 2: every job is first split one / two levels into sub-jobs
+// (nq_finish.hpp), the sub-jobs go into a second LDS queue of NQ_SPLIT_QCAP
+// entries (ranked by a block scan, filled and drained in rounds when they do
+// not all fit), and a lane that finishes one takes the next unclaimed entry
+// from an LDS counter: which lane walks what varies, the sums do not.
+template <bool G1, int SPLIT>
 __global__ void k_nq_x(const DevCtl* ctl, const NQNode* pool, NQNode* childbuf,
                        uint32_t* blockCounts, unsigned long long* blockSols,
                        unsigned long long* blockExtra, int N, int g, int finish,
@@ -779,23 +784,101 @@ __global__ void k_nq_x(const DevCtl* ctl, const NQNode* pool, NQNode* childbuf,
     NqFlat<NQ_FLAT_LEVELS_DEV> st;
     st.tree = 0;
     st.sol = 0;
-    uint32_t q = threadIdx.x;
-    nq_flat_run<NQ_FLAT_LEVELS_DEV, G1>(
-        st,
-        [&](NqFlat<NQ_FLAT_LEVELS_DEV>& w) {
-          if (q >= njobs) return false;
+    // job ref (local parent id * 32 + k) -> the child's masks, seen from the
+    // row below it (as phase A steps them); returns that row
+    auto job_state = [&](uint32_t e, uint32_t& jc, uint32_t& jd1, uint32_t& jd2) {
+      const uint32_t pi = e >> 5;
+      const NQNode& p = s[pi];
+      jc = pmask[pi][0];
+      jd1 = pmask[pi][1];
+      jd2 = pmask[pi][2];
+      nq_step_down(jc, jd1, jd2, 1u << p.board[e & 31u], msk);
+      return static_cast<int>(p.depth) + 1;
+    };
+    if constexpr (SPLIT == 0) {
+      uint32_t q = threadIdx.x;
+      nq_flat_run<NQ_FLAT_LEVELS_DEV, G1>(
+          st,
+          [&](NqFlat<NQ_FLAT_LEVELS_DEV>& w) {
+            if (q >= njobs) return false;
+            const uint32_t e = jobq[q];
+            q += BLOCK;
+            uint32_t jc, jd1, jd2;
+            const int row = job_state(e, jc, jd1, jd2);
+            w.template load<G1>(jc, jd1, jd2, row, N, msk, g);
+            return true;
+          },
+          msk, g);
+    } else {
+      // phase C1, split: thread t counts the sub-jobs of jobs t, t + 256, ...
+      // (and the nodes of the rows it enumerates); a block scan per row of 256
+      // jobs turns the counts into queue offsets, in job order.
+      static_assert(EMIT_TILE * NQ_SPLIT_FANOUT_MAX < 65536, "sub-job offsets are 16-bit");
+      __shared__ uint16_t joboff[EMIT_TILE + 2];
+      __shared__ uint32_t subq[NQ_SPLIT_QCAP];
+      __shared__ uint32_t qhead;
+      uint32_t run = 0;
+      for (uint32_t q0 = 0; q0 < njobs; q0 += BLOCK) {  // block-uniform trip count
+        const uint32_t q = q0 + threadIdx.x;
+        uint32_t n = 0;
+        if (q < njobs) {
+          uint32_t jc, jd1, jd2, nodes = 0;
+          const int row = job_state(jobq[q], jc, jd1, jd2);
+          n = nq_split_job<G1, false>(jc, jd1, jd2, nq_split_levels(SPLIT, N - row), msk, g,
+                                      nodes, [](uint32_t, uint32_t, uint32_t) {});
+          extra += nodes;
+        }
+        uint32_t tot;
+        const uint32_t pre = block_excl_scan(n, tot);
+        if (q < njobs) joboff[q] = static_cast<uint16_t>(run + pre);
+        run += tot;
+      }
+      if (threadIdx.x == 0) joboff[njobs] = static_cast<uint16_t>(run);
+      __syncthreads();
+      // phase C2, rounds: the longest run of jobs whose sub-jobs fit the queue
+      // is written out and drained; a lane that finishes a sub-job takes the
+      // next unclaimed entry (one LDS add per wave and fetch).
+      const unsigned long long lt = (1ull << lane) - 1ull;
+      for (uint32_t jb = 0; jb < njobs;) {  // block-uniform: je comes from LDS alone
+        const uint32_t je = nq_round_end(joboff, jb, njobs, NQ_SPLIT_QCAP);
+        const uint32_t base = joboff[jb];
+        const uint32_t nsub = joboff[je] - base;
+        for (uint32_t q = jb + threadIdx.x; q < je; q += BLOCK) {
           const uint32_t e = jobq[q];
-          q += BLOCK;
-          const uint32_t pi = e >> 5;
-          const NQNode& p = s[pi];
-          const uint32_t b = 1u << p.board[e & 31u];
-          // the child's masks, seen from the row below it (as phase A steps them)
-          w.template load<G1>(pmask[pi][0] | b, ((pmask[pi][1] | b) << 1) & msk,
-                              (pmask[pi][2] | b) >> 1, p.depth + 1, N, msk, g);
-          return true;
-        },
-        msk, g);
-    // 32-bit per-lane counters: at most 4 jobs of <= 109,600 nodes each
+          uint32_t jc, jd1, jd2, nodes = 0;
+          const int row = job_state(e, jc, jd1, jd2);
+          uint32_t w = joboff[q] - base;
+          nq_split_job<true, true>(jc, jd1, jd2, nq_split_levels(SPLIT, N - row), msk, 1, nodes,
+                                   [&](uint32_t nc, uint32_t c1, uint32_t c2) {
+                                     subq[w++] = nq_sub_encode(e, nc, c1, c2);
+                                   });
+        }
+        if (threadIdx.x == 0) qhead = 0;
+        __syncthreads();
+        nq_flat_run<NQ_FLAT_LEVELS_DEV, G1>(
+            st,
+            [&](NqFlat<NQ_FLAT_LEVELS_DEV>& w) {
+              // the lanes that ask together (EXEC is partial here) share one add
+              const unsigned long long ask = __ballot(1);
+              const uint32_t rank = static_cast<uint32_t>(__popcll(ask & lt));
+              uint32_t got = 0;
+              if (rank == 0) got = atomicAdd(&qhead, static_cast<uint32_t>(__popcll(ask)));
+              got = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(got)));
+              const uint32_t qi = got + rank;
+              if (qi >= nsub) return false;
+              const uint32_t e = subq[qi];
+              uint32_t jc, jd1, jd2;
+              const int row = job_state(nq_sub_ref(e), jc, jd1, jd2);
+              nq_sub_load<G1>(w, e, jc, jd1, jd2, row, N, msk, g);
+              return true;
+            },
+            msk, g);
+        __syncthreads();  // the next round rewrites subq and qhead
+        jb = je;
+      }
+    }
+    // 32-bit per-lane counters: a block's whole queue is at most 1024 jobs of
+    // <= 109,600 nodes each, below 2^32, whichever lane walks what
     extra += st.tree;
     sols += st.sol;
   }
@@ -1754,16 +1837,17 @@ int devpool_stride(int lbk) {
 
 void launch_nq_x(const DevCtl* ctl, const NQNode* pool, NQNode* childbuf,
                  uint32_t* blockCounts, unsigned long long* blockSols,
-                 unsigned long long* blockExtra, int N, int g, int finish,
+                 unsigned long long* blockExtra, int N, int g, int finish, int split,
                  unsigned long long m, unsigned long long M, hipStream_t s) {
+  auto go = [&](auto kernel) {
+    hipLaunchKernelGGL(kernel, dim3(devpool_grid(M, N, 1)), dim3(BLOCK), 0, s, ctl, pool,
+                       childbuf, blockCounts, blockSols, blockExtra, N, g, finish, m, M);
+  };
   if (g == 1)
-    hipLaunchKernelGGL((k_nq_x<true>), dim3(devpool_grid(M, N, 1)), dim3(BLOCK), 0, s, ctl,
-                       pool, childbuf, blockCounts, blockSols, blockExtra, N, g, finish, m,
-                       M);
+    split <= 0 ? go(k_nq_x<true, 0>) : split == 1 ? go(k_nq_x<true, 1>) : go(k_nq_x<true, 2>);
   else
-    hipLaunchKernelGGL((k_nq_x<false>), dim3(devpool_grid(M, N, 1)), dim3(BLOCK), 0, s, ctl,
-                       pool, childbuf, blockCounts, blockSols, blockExtra, N, g, finish, m,
-                       M);
+    split <= 0 ? go(k_nq_x<false, 0>) : split == 1 ? go(k_nq_x<false, 1>)
+                                                   : go(k_nq_x<false, 2>);
 }
 
 template <int MM>

@@ -166,4 +166,119 @@ NQ_HD inline void nq_flat_run(NqFlat<LEVELS>& st, Next&& next, uint32_t msk, int
   }
 }
 
+// ---------------------------------------------------------------------------
+// Sub-jobs: a finisher job split below its root, so that a block's queue holds
+// several short walks per lane instead of one long one (k_nq_x SPLIT >= 1, and
+// the CPU entry point nq_finish_block_cpu: the same functions, run in sequence).
+//
+// A job with `rem` rows left is split L = min(S, rem - 1) levels: the split
+// pass enumerates the candidates of the job's first L rows (none of them the
+// bottom row), counts them as tree nodes, and every candidate of the last
+// enumerated row becomes one sub-job, the subtree below it. L == 0 keeps the
+// job whole. A sub-job's root may be the bottom row; NqFlat::load counts it.
+// ---------------------------------------------------------------------------
+
+// Queue capacity: the largest that keeps k_nq_x's LDS (11,456 B + 2,052 B of
+// offsets + the queue) within 20,480 B, i.e. eight blocks per CU; 2048 entries
+// need fewer second rounds but leave seven blocks and measured slower
+// (BASELINE.md "Split finisher jobs"). -DGATS_NQ_QCAP=n builds another size.
+#ifndef GATS_NQ_QCAP
+#define GATS_NQ_QCAP 1728
+#endif
+inline constexpr int NQ_SPLIT_MAX = 2;                // deepest split
+inline constexpr int NQ_SPLIT_DEFAULT = 2;            // GATS_NQ_SPLIT's default
+inline constexpr int NQ_SPLIT_QCAP = GATS_NQ_QCAP;    // the kernel's sub-job queue [entries]
+inline constexpr uint32_t NQ_SPLIT_FANOUT_MAX = 56;   // 8 * 7 sub-jobs of an 8-row job at S = 2
+static_assert(NQ_SPLIT_QCAP >= static_cast<int>(NQ_SPLIT_FANOUT_MAX), "one job must fit the queue");
+
+NQ_HD inline int nq_split_levels(int S, int rem) {
+  const int l = rem - 1 < S ? rem - 1 : S;
+  return l < 0 ? 0 : l;
+}
+
+// Queue entry: | ncols 2 | job reference 14 (local parent id * 32 + k) | c1 5 | c2 5 |
+// ncols is the number of columns (0..2) that lead from the job to the sub-job.
+NQ_HD inline uint32_t nq_sub_encode(uint32_t ref, uint32_t ncols, uint32_t c1, uint32_t c2) {
+  return ncols << 24 | ref << 10 | c1 << 5 | c2;
+}
+NQ_HD inline uint32_t nq_sub_ref(uint32_t e) { return (e >> 10) & 0x3fffu; }
+NQ_HD inline uint32_t nq_sub_ncols(uint32_t e) { return e >> 24; }
+NQ_HD inline uint32_t nq_sub_c1(uint32_t e) { return (e >> 5) & 31u; }
+NQ_HD inline uint32_t nq_sub_c2(uint32_t e) { return e & 31u; }
+
+// The masks below a queen on `bit`, seen from the next row (NqFlat::load's form).
+NQ_HD inline void nq_step_down(uint32_t& c, uint32_t& d1, uint32_t& d2, uint32_t bit,
+                               uint32_t msk) {
+  c |= bit;
+  d1 = ((d1 | bit) << 1) & msk;
+  d2 = (d2 | bit) >> 1;
+}
+
+// Split the job (c, d1, d2) L levels. Returns its number of sub-jobs and adds
+// the candidates of the enumerated rows to `nodes`. With EMIT, emit(ncols, c1,
+// c2) is called once per sub-job, c1-major in ascending columns: that order is
+// the queue order. G1 == false evaluates every enumerated row's free mask g
+// times; the counting pass does that, the writing pass (EMIT) only re-derives.
+template <bool G1, bool EMIT, class Emit>
+NQ_HD inline uint32_t nq_split_job(uint32_t c, uint32_t d1, uint32_t d2, int L, uint32_t msk,
+                                   int g, uint32_t& nodes, Emit&& emit) {
+  if (L == 0) {
+    if (EMIT) emit(0u, 0u, 0u);
+    return 1;
+  }
+  const uint32_t occ0 = c | d1 | d2;
+  uint32_t f0 = G1 ? (~occ0 & msk) : nq_free_occ_g(occ0, msk, g);
+  uint32_t n = static_cast<uint32_t>(__builtin_popcount(f0));
+  nodes += n;
+  if (L == 1) {
+    if (EMIT)
+      for (; f0; f0 &= f0 - 1) emit(1u, static_cast<uint32_t>(__builtin_ctz(f0)), 0u);
+    return n;
+  }
+  n = 0;
+  for (; f0; f0 &= f0 - 1) {
+    uint32_t c1c = c, c1d1 = d1, c1d2 = d2;
+    nq_step_down(c1c, c1d1, c1d2, f0 & (0u - f0), msk);
+    const uint32_t occ1 = c1c | c1d1 | c1d2;
+    uint32_t f1 = G1 ? (~occ1 & msk) : nq_free_occ_g(occ1, msk, g);
+    n += static_cast<uint32_t>(__builtin_popcount(f1));
+    if (EMIT) {
+      const uint32_t c1 = static_cast<uint32_t>(__builtin_ctz(f0));
+      for (; f1; f1 &= f1 - 1) emit(2u, c1, static_cast<uint32_t>(__builtin_ctz(f1)));
+    }
+  }
+  nodes += n;
+  return n;
+}
+
+// Start the walk of sub-job `e` of the job (c, d1, d2) whose first empty row
+// is `row`: re-step the job's masks through the entry's columns, then load.
+template <bool G1, int LEVELS>
+NQ_HD inline void nq_sub_load(NqFlat<LEVELS>& w, uint32_t e, uint32_t c, uint32_t d1,
+                              uint32_t d2, int row, int N, uint32_t msk, int g) {
+  const uint32_t nc = nq_sub_ncols(e);
+  if (nc >= 1) nq_step_down(c, d1, d2, 1u << nq_sub_c1(e), msk);
+  if (nc >= 2) nq_step_down(c, d1, d2, 1u << nq_sub_c2(e), msk);
+  w.template load<G1>(c, d1, d2, row + static_cast<int>(nc), N, msk, g);
+}
+
+// Rounds cut. off[0..njobs] are the jobs' exclusive sub-job offsets in queue
+// order (off[njobs] = all of them). A round takes the longest run of jobs
+// [jb, je) whose sub-jobs fit `qcap` entries; returns je (== jb only when job
+// jb alone does not fit). Every thread of a block computes the same je.
+template <class OffT>
+NQ_HD inline uint32_t nq_round_end(const OffT* off, uint32_t jb, uint32_t njobs, uint32_t qcap) {
+  const uint32_t lim = static_cast<uint32_t>(off[jb]) + qcap;
+  if (static_cast<uint32_t>(off[njobs]) <= lim) return njobs;  // the usual case: one round
+  uint32_t lo = jb, hi = njobs;  // off[lo] <= lim < off[hi]
+  while (hi - lo > 1) {
+    const uint32_t mid = (lo + hi) >> 1;
+    if (static_cast<uint32_t>(off[mid]) <= lim)
+      lo = mid;
+    else
+      hi = mid;
+  }
+  return lo;
+}
+
 }  // namespace gats
