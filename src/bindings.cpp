@@ -13,6 +13,8 @@
 #include "nq_finish.hpp"
 #include "pool.hpp"
 #include "search_host.hpp"
+#include "share_selftest.hpp"
+#include "slice_share.hpp"
 #include "taillard.hpp"
 
 namespace py = pybind11;
@@ -513,6 +515,20 @@ py::dict loop_out_to_dict(const DevpoolLoopOut<NodeT>& o) {
       t["from_spill"] = r.from_spill;
       t["init_size"] = r.size_before;
       t["leftover"] = r.size_after;
+      t["best"] = r.best;
+    } else if (r.kind == DevLoopRec::DONATE) {
+      t["kind"] = "donate";
+      t["size_before"] = r.size_before;
+      t["size_after"] = r.size_after;
+      t["best"] = r.best;
+      t["taken"] = r.outcome == static_cast<int>(Donation::TAKEN);
+      t["withdrawn"] = r.outcome == static_cast<int>(Donation::WITHDRAWN);
+      t["moved"] = nodes;
+    } else if (r.kind == DevLoopRec::TAKE) {
+      t["kind"] = "take";
+      t["size"] = r.size_before;
+      t["best"] = r.best;
+      t["nodes"] = nodes;
     } else if (r.kind == DevLoopRec::SPILL) {
       t["kind"] = "spill";
       t["size_before"] = r.size_before;
@@ -602,6 +618,102 @@ py::dict pool_selftest() {
   d["bulk"] = p.popBackBulk(10, 500, buf.data());               // -> 500
   d["size_final"] = p.size();
   return d;
+}
+
+// `threads` slice threads over one SliceShare (driver-level tests): a list of
+// loop_out_to_dict results, one per thread.
+template <class NodeT>
+py::list share_outs_to_list(const std::vector<DevpoolLoopOut<NodeT>>& outs) {
+  py::list l;
+  for (const auto& o : outs) l.append(loop_out_to_dict(o));
+  return l;
+}
+
+py::list nq_devpool_share_py(const py::bytes& nodes, int N, int g, int finish, long long m,
+                             long long chunk, long long capacity, long long max_batches,
+                             int threads, long long donate_floor, long long await_idle_ms,
+                             int device) {
+  auto v = nodes_from_bytes<NQNode>(nodes);
+  const unsigned long long mv = loop_arg(m, "m"), cv = loop_arg(chunk, "chunk"),
+                           cap = loop_arg(capacity, "capacity");
+  validate_devpool_loop(v.size(), cv, cap, max_batches);
+  validate_devpool_share(threads, donate_floor, await_idle_ms);
+  std::vector<DevpoolLoopOut<NQNode>> o;
+  {
+    py::gil_scoped_release rel;
+    o = nq_devpool_share(v, N, g, finish, mv, cv, cap, static_cast<int>(max_batches), threads,
+                         static_cast<unsigned long long>(donate_floor),
+                         static_cast<int>(await_idle_ms), device);
+  }
+  return share_outs_to_list(o);
+}
+
+py::list pfsp_devpool_share_py(const py::bytes& nodes, int inst, const std::string& lb, int best,
+                               long long m, long long chunk, long long capacity,
+                               long long max_batches, const std::string& br, int threads,
+                               long long donate_floor, long long await_idle_ms, int device) {
+  auto v = nodes_from_bytes<PFSPNode>(nodes);
+  const unsigned long long mv = loop_arg(m, "m"), cv = loop_arg(chunk, "chunk"),
+                           cap = loop_arg(capacity, "capacity");
+  validate_devpool_loop(v.size(), cv, cap, max_batches);
+  validate_devpool_share(threads, donate_floor, await_idle_ms);
+  std::vector<DevpoolLoopOut<PFSPNode>> o;
+  {
+    py::gil_scoped_release rel;
+    o = pfsp_devpool_share(v, inst, lb, best, mv, cv, cap, static_cast<int>(max_batches), br,
+                           threads, static_cast<unsigned long long>(donate_floor),
+                           static_cast<int>(await_idle_ms), device);
+  }
+  return share_outs_to_list(o);
+}
+
+// The donation protocol (slice_share.hpp) on plain threads over a fake pool
+// (unit-test helper); the scenarios are in share_selftest.hpp.
+py::dict share_out_to_dict(const share_test::Out& o) {
+  py::dict d;
+  py::list offers, takes;
+  for (const auto& f : o.offers) {
+    py::dict t;
+    static const char* names[] = {"none", "taken", "withdrawn", "abandoned"};
+    t["outcome"] = names[f.outcome];
+    t["set_calls"] = f.set_calls;
+    t["size_after"] = f.size_after;
+    t["idle_after"] = f.idle_after;
+    offers.append(t);
+  }
+  for (const auto& k : o.takes) takes.append(py::make_tuple(k.thief, k.offset, k.n, k.best));
+  d["offers"] = offers;
+  d["takes"] = takes;
+  d["returned_false"] = o.returned_false;
+  d["idle_reached"] = o.idle_reached;
+  d["ms"] = o.ms;
+  return d;
+}
+
+py::dict share_selftest(const std::string& scenario, unsigned long long size,
+                        unsigned long long floor_sz, int thieves, int offers, bool pending,
+                        bool overflow, int best, bool one_each, unsigned long long size_b,
+                        int deadline_ms, int runners, bool by_exception) {
+  if (size > (1ull << 24) || size_b > (1ull << 24) || thieves < 0 || thieves > 8 || offers < 0 ||
+      offers > 64 || runners < 1 || runners > 8 || deadline_ms < 1 || deadline_ms > 2000)
+    throw std::invalid_argument("share_selftest: argument out of range");
+  share_test::Out o;
+  {
+    py::gil_scoped_release rel;
+    if (scenario == "basic")
+      o = share_test::basic(size, floor_sz, thieves, offers, pending, overflow, best, one_each);
+    else if (scenario == "two_donors")
+      o = share_test::two_donors(size, size_b, floor_sz);
+    else if (scenario == "withdraw")
+      o = share_test::withdraw(size, floor_sz);
+    else if (scenario == "deadline")
+      o = share_test::deadline(size, floor_sz, deadline_ms);
+    else if (scenario == "termination")
+      o = share_test::termination(runners, by_exception);
+    else
+      throw std::invalid_argument("share_selftest: unknown scenario");
+  }
+  return share_out_to_dict(o);
 }
 
 }  // namespace
@@ -847,7 +959,23 @@ PYBIND11_MODULE(_core, mod) {
           py::arg("max_batches") = 0, py::arg("br") = "fwd",
           py::arg("lower_best_at") = py::none(), py::arg("device") = 0);
 
+  mod.def("nq_devpool_share", &nq_devpool_share_py, py::arg("nodes"), py::arg("N"),
+          py::arg("g") = 1, py::arg("finish") = 8, py::arg("m") = 25, py::arg("chunk") = 256,
+          py::arg("capacity") = 1 << 16, py::arg("max_batches") = 0, py::arg("threads") = 2,
+          py::arg("donate_floor") = 0, py::arg("await_idle_ms") = 0, py::arg("device") = 0);
+  mod.def("pfsp_devpool_share", &pfsp_devpool_share_py, py::arg("nodes"), py::arg("inst"),
+          py::arg("lb"), py::arg("best"), py::arg("m") = 25, py::arg("chunk") = 256,
+          py::arg("capacity") = 1 << 16, py::arg("max_batches") = 0, py::arg("br") = "fwd",
+          py::arg("threads") = 2, py::arg("donate_floor") = 0, py::arg("await_idle_ms") = 0,
+          py::arg("device") = 0);
+
   mod.def("pool_selftest", &pool_selftest);
+  mod.def("donation_floor", &donation_floor, py::arg("m"));
+  mod.def("share_selftest", &share_selftest, py::arg("scenario"), py::arg("size") = 0,
+          py::arg("floor") = 0, py::arg("thieves") = 1, py::arg("offers") = 1,
+          py::arg("pending") = false, py::arg("overflow") = false, py::arg("best") = 0,
+          py::arg("one_each") = false, py::arg("size_b") = 0, py::arg("deadline_ms") = 40,
+          py::arg("runners") = 1, py::arg("by_exception") = false);
   // pure policy helpers (CPU-unit-testable): kernel geometry selection and
   // the devpool expansion-chunk clamp
   mod.def("devpool_lbk_geom", &devpool_lbk_geom, py::arg("lbk"), py::arg("machines"));

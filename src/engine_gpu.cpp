@@ -37,6 +37,7 @@
 #include "gpu_api.hpp"
 #include "nq_finish.hpp"
 #include "search_host.hpp"
+#include "slice_share.hpp"
 #include "taillard.hpp"
 
 namespace gats {
@@ -653,125 +654,8 @@ struct SliceOut {
 // quiescent until the thief's D2D copy acks). Steal-half + the >=2m donor
 // threshold mirror the reference's stealing rule (Pool_par.chpl:153-165);
 // all waits are bounded, and a waiter exits once no runner remains.
-struct SliceShare {
-  std::mutex mu;
-  std::condition_variable cv;
-  int idle = 0;     // threads waiting for donated work
-  int runners = 0;  // threads currently inside a devpool loop
-  bool offer_ready = false;
-  bool offer_claimed = false;  // a thief took the pointer and is copying
-  bool offer_taken = false;    // the thief's D2D copy completed
-  const void* offer_src = nullptr;  // device ptr to the donated node range
-  unsigned long long offer_n = 0;
-  int offer_best = 0;
-};
-
-// Steal-share helpers for a slice thread.
-// Donor side: runs at readback boundaries (stream idle); carves the BACK half
-// of the live pool when someone is waiting and the pool holds >= 2m nodes,
-// then blocks (bounded waits) until the thief's D2D copy acks.
-template <class NodeT>
-static void donate_if_wanted(SliceShare* share, DevCtl* host_ctl, DevCtl* ctl_d,
-                             NodeT* pool_d, unsigned long long m, hipStream_t s) {
-  static const bool off = std::getenv("GATS_NO_DONATE") != nullptr;  // bisect knob
-  if (off) return;
-  if (!share || host_ctl->overflow) return;
-  // donation floor: a half-pool must be a worthwhile work grant (the thief
-  // pays ~1 ms of engine start-up) — 2m alone (the reference's steal
-  // threshold) caused donation thrash on large searches
-  const unsigned long long floor_sz = std::max<unsigned long long>(2 * m, 1u << 16);
-  if (host_ctl->size < floor_sz) return;
-  if (share->idle == 0) return;  // racy fast path; rechecked under the lock
-  std::unique_lock<std::mutex> lock(share->mu);
-  if (share->idle == 0 || share->offer_ready) return;
-  const unsigned long long half = host_ctl->size / 2;
-  const unsigned long long newsize = host_ctl->size - half;
-  // the stream is idle (caller synced), so rewriting ctl[0].size is safe
-  HIP_CHECK(hipMemcpyAsync(&ctl_d->size, &newsize, sizeof(newsize), hipMemcpyHostToDevice,
-                           s));
-  HIP_CHECK(hipStreamSynchronize(s));
-  share->offer_src = pool_d + newsize;
-  share->offer_n = half;
-  share->offer_best = host_ctl->best;
-  share->offer_ready = true;
-  share->offer_claimed = false;
-  share->offer_taken = false;
-  share->cv.notify_all();
-  const auto deadline = std::chrono::steady_clock::now() + std::chrono::seconds(10);
-  while (!share->offer_taken) {
-    if (!share->offer_claimed && share->idle == 0) {
-      // every waiter left (e.g. threw): withdraw the offer, restore the pool
-      share->offer_ready = false;
-      const unsigned long long restore = host_ctl->size;
-      HIP_CHECK(hipMemcpyAsync(&ctl_d->size, &restore, sizeof(restore),
-                               hipMemcpyHostToDevice, s));
-      HIP_CHECK(hipStreamSynchronize(s));
-      return;
-    }
-    if (share->offer_claimed && std::chrono::steady_clock::now() > deadline) {
-      // thief died mid-copy (an exception is already propagating): give the
-      // nodes up rather than double-count them
-      share->offer_ready = false;
-      host_ctl->size = newsize;
-      return;
-    }
-    share->cv.wait_for(lock, std::chrono::milliseconds(20));
-  }
-  share->offer_ready = false;
-  host_ctl->size = newsize;  // keep the loop's own view consistent
-}
-
-// Thief side: returns true with (src, n, best) filled when donated work was
-// claimed (caller must D2D-copy it and ack via ack_taken), false when no
-// runner remains. Caller holds no lock.
-struct StolenWork {
-  const void* src = nullptr;
-  unsigned long long n = 0;
-  int best = 0;
-};
-
-static bool wait_for_work(SliceShare& share, StolenWork& w) {
-  std::unique_lock<std::mutex> lock(share.mu);
-  share.idle++;
-  while (true) {
-    if (share.offer_ready && !share.offer_claimed) {
-      w.src = share.offer_src;
-      w.n = share.offer_n;
-      w.best = share.offer_best;
-      share.offer_claimed = true;  // ack via ack_taken after the copy
-      share.idle--;
-      return true;
-    }
-    if (share.runners == 0) {
-      share.idle--;
-      return false;
-    }
-    share.cv.wait_for(lock, std::chrono::milliseconds(20));
-  }
-}
-
-static void ack_taken(SliceShare& share) {
-  std::lock_guard<std::mutex> lock(share.mu);
-  share.offer_taken = true;
-  share.cv.notify_all();
-}
-
-struct RunnerScope {
-  SliceShare* s;
-  explicit RunnerScope(SliceShare* share) : s(share) {
-    if (s) {
-      std::lock_guard<std::mutex> l(s->mu);
-      s->runners++;
-    }
-  }
-  ~RunnerScope() {
-    if (s) {
-      std::lock_guard<std::mutex> l(s->mu);
-      s->runners--;
-      s->cv.notify_all();
-    }
-  }
-};
+// SliceShare, the floor and both sides of the handshake live in
+// slice_share.hpp (no HIP there); devpool_thread supplies the device actions.
 
 // What a slice thread's readback and spill hooks see: the host copy of the
 // live control block, its device address, the thread's pool and stream (idle
@@ -810,11 +694,20 @@ static void carve_back_half(const SliceReadback<NodeT>& rb, std::mutex* dest_mu,
 }
 
 // What the loop-driver test entry points add to a slice thread: the chunk cap
-// taken as given, a batch limit per loop call and the trace sink.
+// taken as given, a batch limit per loop call and the trace sink (donations
+// and takes are recorded in it too). With a SliceShare: `donate_floor`
+// replaces donation_floor(m) (0 = the real floor), and at a readback whose
+// pool is at or above the floor the thread first waits at most
+// `await_idle_ms` until each of the `threads` threads of the share is either
+// running or waiting for work (await_idle), so that a search of a few
+// milliseconds donates for certain.
 struct DevpoolThreadTest {
   unsigned long long chunk = 0;
   int max_batches = 0;
   DevLoopTrace* trace = nullptr;
+  unsigned long long donate_floor = 0;
+  int await_idle_ms = 0;
+  int threads = 1;
 };
 
 // Queue-driven slice thread: allocates its device buffers once, then keeps
@@ -857,8 +750,39 @@ static SliceOut devpool_thread(const Problem& problem,
     const DevIterPolicy it = devpool_iter_policy(Mc, bound, P.per, P.lbg, presum);
     P.enqueue(bufs, bufs.ctl.p + parity, bufs.ctl.p + (1 - parity), m, it.Mi, it.ps, stream.s);
   };
+  // Donor side of SliceShare: runs at readback boundaries (stream idle).
+  auto donate = [&](DevCtl* hc, DevCtl* live) {
+    static const bool off = std::getenv("GATS_NO_DONATE") != nullptr;  // bisect knob
+    if (off || !share) return;
+    const unsigned long long floor_sz =
+        (test && test->donate_floor) ? test->donate_floor : donation_floor(m);
+    if (test && test->await_idle_ms > 0 && !hc->overflow && hc->size >= floor_sz)
+      await_idle(*share, test->threads, test->await_idle_ms);
+    const unsigned long long before = hc->size;
+    bool traced = false;
+    // the stream is idle (caller synced), so rewriting the live size is safe
+    auto set_size = [&](unsigned long long x) {
+      HIP_CHECK(hipMemcpyAsync(&live->size, &x, sizeof(x), hipMemcpyHostToDevice, stream.s));
+      HIP_CHECK(hipStreamSynchronize(stream.s));
+      if (trace && x < before) {  // the carve: the offer is not published yet
+        trace->recs.emplace_back();
+        DevLoopRec& rec = trace->recs.back();
+        rec.kind = DevLoopRec::DONATE;
+        rec.size_before = before;
+        rec.best = hc->best;
+        traced = true;
+        trace_nodes(*trace, rec, bufs.pool.p + x, before - x, /*on_device=*/true, stream.s);
+      }
+    };
+    const Donation d = donate_if_wanted(share, hc->size, hc->best, hc->overflow != 0,
+                                        bufs.pool.p, floor_sz, set_size);
+    if (traced) {
+      trace->recs.back().size_after = hc->size;
+      trace->recs.back().outcome = static_cast<int>(d);
+    }
+  };
   ReadbackHook hook = [&](DevCtl* hc, DevCtl* live) {
-    donate_if_wanted(share, hc, live, bufs.pool.p, m, stream.s);
+    donate(hc, live);
     if (on_readback) on_readback({hc, live, bufs.pool.p, stream.s, r});
   };
   ReadbackHook spill = [&](DevCtl* hc, DevCtl* live) {
@@ -902,11 +826,11 @@ static SliceOut devpool_thread(const Problem& problem,
     const int sb_now =
         shared_best ? shared_best->load(std::memory_order_relaxed) : init_best;
     ctl.best = sb_now < init_best ? sb_now : init_best;
+    if (trace) trace->recs[run_rec].best = ctl.best;
     upload_ctl_pair(bufs.ctl.p, ctl, stream.s);
     r.h2d += 2;
     r.h2d_bytes += 2 * sizeof(DevCtl);
     cfg.init_size = init_size;
-    RunnerScope runner(share);
     const DevCtl fin = run_devpool_loop(stream.s, bufs.ctl.p, cfg, iter, r, shared_best,
                                         hook, spill);
     out.fin.tree += fin.tree;
@@ -950,6 +874,10 @@ static SliceOut devpool_thread(const Problem& problem,
                              hipMemcpyHostToDevice, stream.s));
     r.h2d++;
     r.h2d_bytes += nodes.size() * sizeof(NodeT);
+    // a runner from here until the spilled stack is re-run too: with one
+    // scope per run_pool call a waiter that looked between two of them saw no
+    // runner and left for good while this thread still had nodes to share
+    RunnerScope runner(share);
     run_pool(nodes.size(), best0);
     drain_spilled();
   }
@@ -963,6 +891,15 @@ static SliceOut devpool_thread(const Problem& problem,
                              stream.s));
     HIP_CHECK(hipStreamSynchronize(stream.s));
     ack_taken(*share);
+    if (trace) {  // what arrived, read from this thread's own pool
+      trace->recs.emplace_back();
+      DevLoopRec& rec = trace->recs.back();
+      rec.kind = DevLoopRec::TAKE;
+      rec.size_before = rec.size_after = w.n;
+      rec.best = w.best;
+      trace_nodes(*trace, rec, bufs.pool.p, w.n, /*on_device=*/true, stream.s);
+    }
+    RunnerScope runner(share);  // as above
     run_pool(w.n, w.best);
     drain_spilled();
   }
@@ -1517,6 +1454,112 @@ DevpoolLoopOut<PFSPNode> pfsp_devpool_loop(const std::vector<PFSPNode>& nodes, i
   return devpool_loop_traced(
       PfspDevProblem(I, devpool_lbk_geom(lbk_of(lb_from_string(lb)), I.machines)), nodes, best,
       m, chunk, capacity, graph, max_batches, &sb, lower_at, lower_to, device);
+}
+
+// Share entry points: `threads` slice threads, one SliceShare, one slice.
+
+void validate_devpool_share(int threads, long long donate_floor, long long await_idle_ms) {
+  if (threads < 2 || threads > 4) throw std::invalid_argument("threads must be in 2..4");
+  if (donate_floor != 0 && donate_floor < 2)
+    throw std::invalid_argument("donate_floor must be 0 (the real floor) or >= 2");
+  if (await_idle_ms < 0 || await_idle_ms > 5000)
+    throw std::invalid_argument("await_idle_ms must be in 0..5000");
+}
+
+// Callers validate first: nothing here runs before their checks passed.
+template <class Problem>
+static std::vector<DevpoolLoopOut<typename Problem::Node>> devpool_share_traced(
+    const Problem& problem, const std::vector<typename Problem::Node>& nodes, int best0,
+    unsigned long long m, unsigned long long chunk, unsigned long long capacity,
+    int max_batches, std::atomic<int>* sb, int threads, unsigned long long donate_floor,
+    int await_idle_ms, int device) {
+  using NodeT = typename Problem::Node;
+  std::vector<DevpoolLoopOut<NodeT>> outs(threads);
+  std::vector<DevpoolThreadTest> tests(threads);
+  const std::vector<std::vector<NodeT>> slices{nodes};
+  std::atomic<int> next_slice{0};
+  SliceShare share;
+  std::vector<SliceOut> sos(threads);
+  std::vector<std::exception_ptr> errs(threads);
+  std::atomic<bool> first_done{false};
+  (void)hipGetLastError();  // drop a stale launch error of an earlier, unchecked call
+  std::vector<std::thread> pool;
+  for (int t = 0; t < threads; t++) {
+    tests[t].chunk = chunk;
+    tests[t].max_batches = max_batches;
+    tests[t].trace = &outs[t].trace;
+    tests[t].donate_floor = donate_floor;
+    tests[t].await_idle_ms = await_idle_ms;
+    tests[t].threads = threads;
+    pool.emplace_back([&, t] {
+      try {
+        sos[t] = devpool_thread(problem, slices, next_slice, best0, static_cast<int>(m),
+                                /*M=*/0, device, capacity, sb, /*allow_graph=*/false, &share,
+                                outs[t].leftover, {}, &tests[t]);
+      } catch (...) {
+        errs[t] = std::current_exception();
+      }
+      if (t == 0) first_done.store(true);
+    });
+    // a thread that reaches wait_for_work before the slice's owner counts as a
+    // runner leaves at once (the engines live with that); here the others
+    // start only once thread 0 runs the slice, or is through with it
+    if (t == 0) {
+      const auto deadline = std::chrono::steady_clock::now() + std::chrono::seconds(5);
+      while (!first_done.load() && std::chrono::steady_clock::now() < deadline) {
+        {
+          std::lock_guard<std::mutex> l(share.mu);
+          if (share.runners > 0) break;
+        }
+        std::this_thread::sleep_for(std::chrono::microseconds(200));
+      }
+    }
+  }
+  for (auto& th : pool) th.join();
+  for (auto& e : errs)
+    if (e) std::rethrow_exception(e);
+  for (int t = 0; t < threads; t++) {
+    DevpoolLoopOut<NodeT>& out = outs[t];
+    out.tree = sos[t].fin.tree;
+    out.sol = sos[t].fin.sol;
+    out.iters = sos[t].diag.gpu_iters;
+    out.best = sos[t].fin.best;
+    out.diag = sos[t].diag;
+    out.trace.pool_d = nullptr;
+  }
+  return outs;
+}
+
+std::vector<DevpoolLoopOut<NQNode>> nq_devpool_share(
+    const std::vector<NQNode>& nodes, int N, int g, int finish, unsigned long long m,
+    unsigned long long chunk, unsigned long long capacity, int max_batches, int threads,
+    unsigned long long donate_floor, int await_idle_ms, int device) {
+  // before any HIP call
+  validate_nq_step(nodes, N, g, finish, m, chunk, capacity, "auto");
+  validate_devpool_loop(nodes.size(), chunk, capacity, max_batches);
+  validate_devpool_share(threads, static_cast<long long>(donate_floor), await_idle_ms);
+  if (m > (1ull << 30)) throw std::invalid_argument("m must be <= 2^30");
+  return devpool_share_traced(NqDevProblem(N, g, finish), nodes, /*best0=*/0, m, chunk,
+                              capacity, max_batches, nullptr, threads, donate_floor,
+                              await_idle_ms, device);
+}
+
+std::vector<DevpoolLoopOut<PFSPNode>> pfsp_devpool_share(
+    const std::vector<PFSPNode>& nodes, int inst, const std::string& lb, int best,
+    unsigned long long m, unsigned long long chunk, unsigned long long capacity,
+    int max_batches, const std::string& br, int threads, unsigned long long donate_floor,
+    int await_idle_ms, int device) {
+  // before any HIP call
+  validate_pfsp_step(nodes, inst, lb, m, chunk, capacity, /*geom=*/-1, "auto", br);
+  validate_devpool_loop(nodes.size(), chunk, capacity, max_batches);
+  validate_devpool_share(threads, static_cast<long long>(donate_floor), await_idle_ms);
+  if (m > (1ull << 30)) throw std::invalid_argument("m must be <= 2^30");
+  if (best < 1) throw std::invalid_argument("best must be >= 1");
+  const PfspInstance& I = pfsp_instance_cached(inst, 1, branching_from_string(br));
+  std::atomic<int> sb{best};
+  return devpool_share_traced(
+      PfspDevProblem(I, devpool_lbk_geom(lbk_of(lb_from_string(lb)), I.machines)), nodes, best,
+      m, chunk, capacity, max_batches, &sb, threads, donate_floor, await_idle_ms, device);
 }
 
 // ---------------------------------------------------------------------------

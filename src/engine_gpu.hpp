@@ -273,14 +273,35 @@ std::vector<DevpoolSnapshot<PFSPNode>> pfsp_devpool_chain(
 // Everything is validated on the host before the first HIP call (the step
 // entry points' checks, capacity <= 2^22 nodes); the trace itself is capped
 // at 2^22 nodes in total (std::runtime_error beyond).
+//
+// Share entry points (nq_devpool_share / pfsp_devpool_share): `threads` (2..4)
+// real slice threads on one device over ONE SliceShare, one shared incumbent
+// and one slice holding all the nodes, graph replay off as in the engines'
+// multi-slice runs; one DevpoolLoopOut per thread. Thread 0 runs the slice; the
+// others start once it counts as a runner and go straight to wait_for_work,
+// and any of them may take and donate from then on. `donate_floor`
+// (0 = donation_floor(m), else >= 2) and `await_idle_ms` (0..5000) are
+// DevpoolThreadTest's knobs. Two more record kinds appear:
+//   DONATE in the donor's trace, after the BATCH whose readback it follows:
+//          size_before, size_after (the kept front; == size_before when the
+//          offer was withdrawn), best = the offered incumbent, outcome (the
+//          Donation value), and the offered nodes read from the pool's back
+//          half after the carve and BEFORE the offer is published;
+//   TAKE   in the thief's trace, before the RUN it starts: the received nodes
+//          read from the thief's own pool after its copy, best = the received
+//          incumbent.
+// RUN records carry in `best` the incumbent the run's control blocks start from.
 struct DevLoopRec {
-  enum Kind { RUN = 0, BATCH = 1, SPILL = 2 };
+  enum Kind { RUN = 0, BATCH = 1, SPILL = 2, DONATE = 3, TAKE = 4 };
   int kind = BATCH;
   int b = 0, parity = 0;
   bool graph = false, captured = false, from_spill = false;
   unsigned long long size_before = 0, size_after = 0;
+  int best = 0;     // RUN / DONATE / TAKE
+  int outcome = 0;  // DONATE: Donation (slice_share.hpp)
   DevpoolStepCtl ctl{};
-  std::vector<unsigned char> nodes;  // BATCH: the pool; SPILL: the moved nodes
+  // BATCH: the pool; SPILL / DONATE: the moved nodes; TAKE: the received ones
+  std::vector<unsigned char> nodes;
 };
 struct DevLoopTrace {
   std::vector<DevLoopRec> recs;
@@ -308,6 +329,16 @@ DevpoolLoopOut<PFSPNode> pfsp_devpool_loop(const std::vector<PFSPNode>& nodes, i
                                            unsigned long long capacity, bool graph,
                                            int max_batches, const std::string& br,
                                            long long lower_at, int lower_to, int device);
+void validate_devpool_share(int threads, long long donate_floor, long long await_idle_ms);
+std::vector<DevpoolLoopOut<NQNode>> nq_devpool_share(
+    const std::vector<NQNode>& nodes, int N, int g, int finish, unsigned long long m,
+    unsigned long long chunk, unsigned long long capacity, int max_batches, int threads,
+    unsigned long long donate_floor, int await_idle_ms, int device);
+std::vector<DevpoolLoopOut<PFSPNode>> pfsp_devpool_share(
+    const std::vector<PFSPNode>& nodes, int inst, const std::string& lb, int best,
+    unsigned long long m, unsigned long long chunk, unsigned long long capacity,
+    int max_batches, const std::string& br, int threads, unsigned long long donate_floor,
+    int await_idle_ms, int device);
 
 std::vector<uint8_t> nq_gpu_labels(int N, int g, const std::vector<NQNode>& nodes,
                                    int device);

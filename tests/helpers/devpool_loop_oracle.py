@@ -37,9 +37,10 @@ BLOCK = 64          # nodes per cached block of SeqCache
 
 
 class Cfg:
-    def __init__(self, m, chunk, per, capacity, graph=True, max_batches=0):
+    def __init__(self, m, chunk, per, capacity, graph=True, max_batches=0, floor=None):
         self.m, self.chunk, self.per, self.capacity = m, chunk, per, capacity
         self.graph, self.max_batches = graph, max_batches
+        self.floor = floor  # share runs: the donation floor in force
         self.growth = chunk * per  # worst-case children per iteration
 
 
@@ -98,10 +99,11 @@ def counts(trace):
                                                for r in trace[:first_spill]))
 
 
-def check_trace(out, cfg, n0):
-    """The decision rules. `out` is an entry point's (or the model's) result,
-    n0 the input pool's node count."""
-    trace = out["trace"]
+def _trace_job(trace, cfg, n0, floor=None):
+    """The decision rules over one job of a slice thread: the run that starts
+    from `n0` nodes (the slice, or a donated half) and the runs that drain its
+    spills. `floor`: the donation floor where "donate" records may occur.
+    Returns the sums the diag counters are made of."""
     runs = runs_of(trace)
     assert runs and not runs[0][0]["from_spill"] and runs[0][0]["init_size"] == n0, runs[0][0]
     stack = 0       # nodes on the spilled stack
@@ -114,13 +116,30 @@ def check_trace(out, cfg, n0):
             stack -= run["init_size"]
         size, batches, par, have_graph = run["init_size"], 0, 0, False
         prev_iters = 0
-        ended = False
-        assert recs and recs[-1]["kind"] == "batch", (w, "a run ends with a batch")
+        prev = None
+        assert recs and recs[-1]["kind"] in ("batch", "donate"), (w, "a run ends with a batch")
+
+        def ended():
+            return size < cfg.m or (cfg.max_batches > 0 and batches >= cfg.max_batches)
         for rec in recs:
             w = ("run", ri, "batch", batches, {k: v for k, v in rec.items()
                                                if k not in ("pool", "moved")})
-            assert not ended, (w, "record after the loop's exit condition held")
             assert rec["size_before"] == size, (w, size)
+            if rec["kind"] == "donate":
+                # the donation check of the readback just before, at most once
+                assert floor is not None, (w, "a donation without a share")
+                assert prev is not None and prev["kind"] == "batch", (w, "not after a readback")
+                assert size >= floor, (w, "a donation below the floor", floor)
+                assert rec["taken"] != rec["withdrawn"], (w, "neither taken nor withdrawn")
+                half = size // 2
+                assert len(rec["moved"]) == half * NODE, (w, len(rec["moved"]))
+                assert rec["best"] == prev["ctl"]["best"], (w, "offered incumbent", prev["ctl"])
+                assert rec["size_after"] == (size - half if rec["taken"] else size), w
+                size = rec["size_after"]
+                prev = rec
+                continue
+            assert not ended(), (w, "record after the loop's exit condition held")
+            prev = rec
             want = batch_len(cfg, size, batches)
             if rec["kind"] == "spill":
                 # only under capacity pressure, only a pool worth halving, never first
@@ -159,21 +178,35 @@ def check_trace(out, cfg, n0):
             batches += 1
             sum_b += b
             size = ctl["size"]
-            ended = size < cfg.m or (cfg.max_batches > 0 and batches >= cfg.max_batches)
-        assert ended, (("run", ri), "the loop left early", size, batches)
+        assert ended(), (("run", ri), "the loop left early", size, batches)
         assert run["leftover"] == size, (("run", ri), run, size)
         leftover_copies += size > 0
         leftover_nodes += size
-        iters += recs[-1]["ctl"]["iters"]
+        iters += prev_iters
     assert stack == 0, ("spilled nodes never re-run", stack)
-    assert len(out["leftover"]) == leftover_nodes * NODE
-    assert out["iters"] == iters, (out["iters"], iters)
+    return dict(sum_b=sum_b, leftover_copies=leftover_copies, leftover_nodes=leftover_nodes,
+                iters=iters, runs=len(runs), batches=len(batches_of(trace)),
+                spills=len(spills_of(trace)))
+
+
+def _check_diag(out, sums, uploads):
+    """The thread's totals and diag counters as sums over its jobs."""
+    t = {k: sum(s[k] for s in sums) for k in sums[0]} if sums else dict.fromkeys(
+        ("sum_b", "leftover_copies", "leftover_nodes", "iters", "runs", "batches", "spills"), 0)
+    assert len(out["leftover"]) == t["leftover_nodes"] * NODE
+    assert out["iters"] == t["iters"], (out["iters"], t["iters"])
     d = out["diag"]
-    assert d["kernel_launch"] == 2 * sum_b, (d, sum_b)
-    assert d["device_to_host"] == len(batches_of(trace)) + len(spills_of(trace)) + \
-        leftover_copies, (d, leftover_copies)
-    assert d["host_to_device"] == 3 * len(runs), d  # the pool and two control blocks
-    assert d["gpu_iters"] == iters, d
+    assert d["kernel_launch"] == 2 * t["sum_b"], (d, t)
+    assert d["device_to_host"] == t["batches"] + t["spills"] + t["leftover_copies"], (d, t)
+    assert d["host_to_device"] == uploads, (d, uploads)
+    assert d["gpu_iters"] == t["iters"], d
+
+
+def check_trace(out, cfg, n0):
+    """The decision rules. `out` is an entry point's (or the model's) result,
+    n0 the input pool's node count."""
+    sums = _trace_job(out["trace"], cfg, n0)
+    _check_diag(out, [sums], 3 * sums["runs"])  # the pool and two control blocks per run
 
 
 class SeqCache:
@@ -211,6 +244,64 @@ def pfsp_seq_fn(core, inst, lb, best, br="fwd"):
     return f
 
 
+def _conserve_job(trace, pool0, seq, cfg, from_batch=0, total=None):
+    """check_conservation over one job (see _trace_job) that starts from
+    `pool0`. A taken donation is a spill whose nodes leave the thread: they are
+    counted as still to do, and the kept front is what the next batch starts
+    from; after a withdrawn one the whole snapshot is. seq None: the byte
+    checks alone. Returns (total, (tree, sol) counted, leftovers, donated)."""
+    stack = b""                 # spilled nodes not yet re-run
+    done_t = done_s = 0         # finished runs' counters
+    left = b""                  # finished runs' leftovers
+    gone = b""                  # donated nodes
+    k = 0
+    for ri, (run, recs) in enumerate(runs_of(trace)):
+        snap = pool0
+        if ri > 0:  # the drained chunk: the top of the stack
+            take = run["init_size"] * NODE
+            assert 0 < take <= len(stack), (ri, take, len(stack))
+            stack, snap = stack[:len(stack) - take], stack[len(stack) - take:]
+        rest = None  # tree / sol of the stack and the leftovers, until they change
+        last = None
+        for rec in recs:
+            if rec["kind"] in ("spill", "donate"):
+                what = rec["kind"]
+                keep = (rec["size_before"] - rec["size_before"] // 2) * NODE
+                assert len(snap) == rec["size_before"] * NODE, (ri, k, "stale snapshot")
+                assert rec["moved"] == snap[keep:], (ri, k, "the %s did not move the back half" % what)
+                if what == "donate" and not rec["taken"]:
+                    continue  # withdrawn: the next readback must find all of snap
+                rest = None
+                snap = snap[:keep]  # the kept prefix; the next readback's conservation holds
+                if what == "spill":
+                    stack += rec["moved"]  # only if the device kept exactly this
+                else:
+                    gone += rec["moved"]
+                continue
+            # b iterations pop at most b * chunk nodes below the old top
+            # (children are pushed above whatever is left): the rest of the
+            # previous pool is still there, byte for byte
+            keep = max(len(snap) - rec["b"] * cfg.chunk * NODE, 0)
+            assert rec["pool"][:keep] == snap[:keep], (ri, k, "un-popped prefix changed", keep // NODE)
+            snap, ctl = rec["pool"], rec["ctl"]
+            last = ctl
+            if k >= from_batch and seq is not None:
+                pt, ps = seq(snap)
+                if rest is None:
+                    (st, ss), (lt, ls), (gt, gs) = seq(stack), seq(left), seq(gone)
+                    rest = (st + lt + gt, ss + ls + gs)
+                got = (done_t + ctl["tree"] + pt + rest[0], done_s + ctl["sol"] + ps + rest[1])
+                if total is None:
+                    total = got
+                assert got == total, ("conservation", "run", ri, "batch", k, got, total,
+                                      dict(ctl), len(snap) // NODE, len(stack) // NODE)
+            k += 1
+        done_t += last["tree"]
+        done_s += last["sol"]
+        left += snap
+    return total, (done_t, done_s), left, gone
+
+
 def check_conservation(out, pool0, seq, cfg, from_batch=0, total=None):
     """At every readback (from global batch index `from_batch` on; `total` is
     then taken at that batch): counted + CPU search of what is left == total.
@@ -221,48 +312,9 @@ def check_conservation(out, pool0, seq, cfg, from_batch=0, total=None):
     Returns the total (tree, sol)."""
     if total is None and from_batch == 0:
         total = seq(pool0)
-    stack = b""                 # spilled nodes not yet re-run
-    done_t = done_s = 0         # finished runs' counters
-    left = b""                  # finished runs' leftovers
-    k = 0
-    for ri, (run, recs) in enumerate(runs_of(out["trace"])):
-        snap = pool0
-        if ri > 0:  # the drained chunk: the top of the stack
-            take = run["init_size"] * NODE
-            assert 0 < take <= len(stack), (ri, take, len(stack))
-            stack, snap = stack[:len(stack) - take], stack[len(stack) - take:]
-        rest = None  # tree / sol of the stack and the leftovers, until they change
-        for rec in recs:
-            if rec["kind"] == "spill":
-                rest = None
-                keep = rec["size_after"] * NODE
-                assert len(snap) == rec["size_before"] * NODE, (ri, k, "stale snapshot")
-                assert rec["moved"] == snap[keep:], (ri, k, "the spill did not move the back half")
-                snap = snap[:keep]  # the kept prefix; the next readback's conservation holds
-                stack += rec["moved"]  # only if the device kept exactly this
-                continue
-            # b iterations pop at most b * chunk nodes below the old top
-            # (children are pushed above whatever is left): the rest of the
-            # previous pool is still there, byte for byte
-            keep = max(len(snap) - rec["b"] * cfg.chunk * NODE, 0)
-            assert rec["pool"][:keep] == snap[:keep], (ri, k, "un-popped prefix changed", keep // NODE)
-            snap, ctl = rec["pool"], rec["ctl"]
-            if k >= from_batch:
-                pt, ps = seq(snap)
-                if rest is None:
-                    (st, ss), (lt, ls) = seq(stack), seq(left)
-                    rest = (st + lt, ss + ls)
-                got = (done_t + ctl["tree"] + pt + rest[0], done_s + ctl["sol"] + ps + rest[1])
-                if total is None:
-                    total = got
-                assert got == total, ("conservation", "run", ri, "batch", k, got, total,
-                                      dict(ctl), len(snap) // NODE, len(stack) // NODE)
-            k += 1
-        done_t += recs[-1]["ctl"]["tree"]
-        done_s += recs[-1]["ctl"]["sol"]
-        left += snap
+    total, done, left, _ = _conserve_job(out["trace"], pool0, seq, cfg, from_batch, total)
     assert left == out["leftover"], "the leftovers are not the runs' final pools"
-    assert (done_t, done_s) == (out["tree"], out["sol"]), (done_t, done_s, out["tree"], out["sol"])
+    assert done == (out["tree"], out["sol"]), (done, out["tree"], out["sol"])
     return total
 
 
@@ -283,25 +335,162 @@ def check_all(out, pool0, seq, cfg, total=None):
 
 
 # ---------------------------------------------------------------------------
+# several slice threads over one SliceShare (nq_devpool_share /
+# pfsp_devpool_share): one result per thread. A thread's trace is a sequence of
+# jobs: the slice (thread 0's first run and the runs draining its spills), then
+# one job per "take" record. "donate" records follow the readback whose
+# donation check made the offer.
+# ---------------------------------------------------------------------------
+
+def jobs_of(trace):
+    """[(take record or None, [the job's run / batch / spill / donate records])]"""
+    jobs = []
+    for rec in trace:
+        if rec["kind"] == "take":
+            jobs.append((rec, []))
+        else:
+            if not jobs:
+                jobs.append((None, []))
+            jobs[-1][1].append(rec)
+    return jobs
+
+
+def donations_of(outs, taken=None):
+    return [r for o in outs for r in o["trace"]
+            if r["kind"] == "donate" and (taken is None or r["taken"] == taken)]
+
+
+def takes_of(outs):
+    return [r for o in outs for r in o["trace"] if r["kind"] == "take"]
+
+
+def share_counts(outs):
+    """Path counters of a share run."""
+    chains = 0  # threads that donated from a job they had taken
+    for o in outs:
+        chains += any(take is not None and any(r["kind"] == "donate" and r["taken"] for r in recs)
+                      for take, recs in jobs_of(o["trace"]))
+    drained = 0  # taken donations made by a run that drains a spilled chunk
+    for o in outs:
+        for run, recs in runs_of([r for r in o["trace"] if r["kind"] != "take"]):
+            drained += run["from_spill"] and sum(r["kind"] == "donate" and r["taken"] for r in recs)
+    return dict(taken=len(donations_of(outs, True)), withdrawn=len(donations_of(outs, False)),
+                drained_donations=drained,
+                takes=len(takes_of(outs)), chains=chains,
+                thieves=sum(any(r["kind"] == "take" for r in o["trace"]) for o in outs),
+                spills=sum(len(spills_of(o["trace"])) for o in outs),
+                batches=sum(len(batches_of(o["trace"])) for o in outs),
+                idle_threads=sum(not o["trace"] for o in outs))
+
+
+def check_share(outs, pool0, seq, cfg, total=None):
+    """Every thread of a share run, whichever thread ran the slice and whichever
+    readbacks donated. cfg.floor is the donation floor in force. seq None (an
+    incumbent that moves during the run): everything but the counts. Returns
+    the total (tree, sol)."""
+    assert cfg.floor is not None and not cfg.graph
+    owners = [i for i, o in enumerate(outs) if o["trace"] and o["trace"][0]["kind"] == "run"]
+    assert len(owners) == 1, ("exactly one thread runs the slice", owners)
+    if seq is not None and total is None:
+        total = seq(pool0)
+    for ti, o in enumerate(outs):
+        sums, left, done = [], b"", (0, 0)
+        jobs = jobs_of(o["trace"])
+        for ji, (take, recs) in enumerate(jobs):
+            w = ("thread", ti, "job", ji)
+            assert (take is None) == (ti == owners[0] and ji == 0), (w, "a job without a take")
+            start = pool0 if take is None else take["nodes"]
+            if take is not None:
+                assert len(start) == take["size"] * NODE and take["size"] > 0, w
+                assert recs and recs[0]["kind"] == "run", (w, "a take is followed by its run")
+                # the run adopts the received incumbent, or a lower shared one
+                assert recs[0]["best"] <= take["best"], (w, "the thief starts above the offer",
+                                                         recs[0]["best"], take["best"])
+            try:
+                sums.append(_trace_job(recs, cfg, len(start) // NODE, cfg.floor))
+                # per-thread conservation: what was taken is this job's pool0,
+                # what was donated counts as still to do
+                _, d, l, _ = _conserve_job(recs, start, seq, cfg,
+                                           total=None if seq is None else seq(start))
+            except AssertionError as e:
+                raise AssertionError((w,) + e.args) from None
+            done = (done[0] + d[0], done[1] + d[1])
+            left += l
+        if not jobs:
+            sums = []
+        takes = sum(take is not None for take, _ in jobs)
+        # a taken pool arrives by a device-to-device copy, which is not counted
+        _check_diag(o, sums, 3 * sum(s["runs"] for s in sums) - takes)
+        assert left == o["leftover"], (ti, "the leftovers are not the runs' final pools")
+        assert done == (o["tree"], o["sol"]), (ti, done, o["tree"], o["sol"])
+    # every taken offer arrives exactly once, in another thread, unchanged
+    open_takes = [(ti, r) for ti, o in enumerate(outs) for r in o["trace"] if r["kind"] == "take"]
+    for ti, o in enumerate(outs):
+        for r in o["trace"]:
+            if r["kind"] != "donate" or not r["taken"]:
+                continue
+            k = next((k for k, (tj, t) in enumerate(open_takes)
+                      if tj != ti and t["nodes"] == r["moved"] and t["best"] == r["best"]), None)
+            assert k is not None, ("a taken offer that no other thread received", ti,
+                                   r["size_before"], r["best"])
+            del open_takes[k]
+    assert not open_takes, ("a take without a donation", [(ti, t["size"], t["best"])
+                                                          for ti, t in open_takes])
+    # global conservation at the end
+    if seq is not None:
+        lt, ls = seq(b"".join(o["leftover"] for o in outs))
+        got = (sum(o["tree"] for o in outs) + lt, sum(o["sol"] for o in outs) + ls)
+        assert got == tuple(total), ("global conservation", got, total)
+    return total
+
+
+def share_model(step_fn, pool0, cfg, best=0, threads=2):
+    """A consistent set of traces, one donation per thread but the last: thread
+    t runs what thread t - 1 gave it. Predicts nothing about a GPU run; it is
+    what check_share is proved on."""
+    outs, pool, b, take = [], pool0, best, None
+    for t in range(threads):
+        if pool is None:
+            outs.append(dict(tree=0, sol=0, best=best, iters=0, leftover=b"", trace=[],
+                             diag=dict(kernel_launch=0, device_to_host=0, host_to_device=0,
+                                       gpu_iters=0)))
+            continue
+        o = loop_model(step_fn, pool, cfg, b, donations=1 if t < threads - 1 else 0)
+        if take is not None:
+            o["trace"].insert(0, take)
+            o["diag"]["host_to_device"] -= 1
+        outs.append(o)
+        pool = None
+        if o["given"]:
+            pool, b = o["given"][0]
+            take = dict(kind="take", size=len(pool) // NODE, best=b, nodes=pool)
+    return outs
+
+
+# ---------------------------------------------------------------------------
 # the model: the decision rules over the step oracle in oracle order
 # ---------------------------------------------------------------------------
 
-def loop_model(step_fn, pool0, cfg, best=0, lower_best_at=None):
+def loop_model(step_fn, pool0, cfg, best=0, lower_best_at=None, donations=0):
     """step_fn(pool, M, tree, sol, iters, best) -> Step (prefix, children,
     ctl) with the pop threshold m built in. Returns what the entry points
-    return. Raises RuntimeError where the driver reports a pool overflow."""
-    trace, leftover = [], b""
+    return. Raises RuntimeError where the driver reports a pool overflow.
+    donations: at most this many readbacks at or above cfg.floor donate (to a
+    thief that is always waiting); the result's "given" lists what left as
+    (nodes, incumbent)."""
+    trace, leftover, given = [], b"", []
     shared = [best]
     tot = dict(tree=0, sol=0, iters=0, kernel_launch=0, d2h=0, h2d=0, k=0, best=best)
     stack = b""
 
     def run_pool(pool, init_best, from_spill):
         nonlocal stack, leftover
-        run = dict(kind="run", from_spill=from_spill, init_size=len(pool) // NODE, leftover=0)
+        run = dict(kind="run", from_spill=from_spill, init_size=len(pool) // NODE, leftover=0,
+                   best=min(init_best, shared[0]))
         trace.append(run)
         tot["h2d"] += 3
         ctl = dict(size=len(pool) // NODE, chunk=0, tree=0, sol=0, iters=0,
-                   best=min(init_best, shared[0]), overflow=0)
+                   best=run["best"], overflow=0)
         batches, par, have_graph = 0, 0, False
         while True:
             size = ctl["size"]
@@ -336,6 +525,14 @@ def loop_model(step_fn, pool0, cfg, best=0, lower_best_at=None):
             if lower_best_at is not None and tot["k"] == lower_best_at[0]:
                 shared[0] = min(shared[0], lower_best_at[1])
             tot["k"] += 1
+            if cfg.floor is not None and ctl["size"] >= cfg.floor and len(given) < donations:
+                size = ctl["size"]
+                keep = size - size // 2
+                moved, pool = pool[keep * NODE:], pool[:keep * NODE]
+                ctl["size"] = keep
+                given.append((moved, ctl["best"]))
+                trace.append(dict(kind="donate", size_before=size, size_after=keep, moved=moved,
+                                  best=ctl["best"], taken=True, withdrawn=False))
             shared[0] = min(shared[0], ctl["best"])
             ctl["best"] = shared[0]  # adoption: written to the live block
             if ctl["size"] < cfg.m or (cfg.max_batches > 0 and batches >= cfg.max_batches):
@@ -354,7 +551,7 @@ def loop_model(step_fn, pool0, cfg, best=0, lower_best_at=None):
         chunk, stack = stack[len(stack) - take:], stack[:len(stack) - take]
         run_pool(chunk, tot["best"], True)
     return dict(tree=tot["tree"], sol=tot["sol"], best=min(tot["best"], shared[0]),
-                iters=tot["iters"], leftover=leftover, trace=trace,
+                iters=tot["iters"], leftover=leftover, trace=trace, given=given,
                 diag=dict(kernel_launch=tot["kernel_launch"], device_to_host=tot["d2h"],
                           host_to_device=tot["h2d"], gpu_iters=tot["iters"]))
 
@@ -527,3 +724,153 @@ def case_counts(out):
 def check_need(n, need, factor=1):
     for k, v in need.items():
         assert n[k] >= factor * v, ("path not reached", k, n[k], "need", factor * v, n)
+
+
+# ---------------------------------------------------------------------------
+# the inputs of tests/test_gpu_devpool_share.py, shared with the CPU tests that
+# prove (on the one-thread model) that each pool reaches its floor with slack
+# ---------------------------------------------------------------------------
+
+REAL_FLOOR = 1 << 16
+
+
+def donation_floor(m):
+    return max(2 * m, REAL_FLOOR)
+
+
+class ShareCase(Case):
+    """A Case run by `threads` slice threads over one SliceShare. floor: the
+    donate_floor argument (0 = the real floor); pools besides Case's "bfs":
+    ("root",), ("random", seed, n, min_depth, max_depth) and ("leaves", n) = n
+    leaf parents (depth == N: popped, nothing pushed). need: share_counts the
+    GPU run must reach; the one-thread model must see at_floor (readbacks with
+    the pool at or above the floor) at least twice as often as need says."""
+
+    def __init__(self, problem, pool, threads=2, floor=0, await_ms=2000, fixed_best=True, **kw):
+        kw.setdefault("graph", False)
+        Case.__init__(self, problem, pool, **kw)
+        self.threads, self.floor, self.await_ms, self.fixed_best = threads, floor, await_ms, fixed_best
+
+    def floor_in_force(self):
+        return self.floor if self.floor else donation_floor(self.m)
+
+    def cfg(self, graph=None):
+        c = Case.cfg(self, False)
+        c.floor = self.floor_in_force()
+        return c
+
+
+def _nq_share(pool, finish, **kw):
+    kw.setdefault("need", dict(taken=1, at_floor=1))
+    return ShareCase("nq", pool, finish=finish, **kw)
+
+
+SHARE_CASES = {
+    # a few hundred random nodes of mixed depth, small floor; finish = 8 takes
+    # nodes from depth N - 8 on in one go, so it gets a larger board and
+    # shallower nodes to have a pool at all
+    "mixed_nq_f-1": _nq_share(("random", 21, 300, 2, 9), -1, N=10, chunk=64, floor=128,
+                              capacity=1 << 14),
+    "mixed_nq_f3": _nq_share(("random", 21, 300, 2, 9), 3, N=10, chunk=64, floor=128,
+                             capacity=1 << 14),
+    "mixed_nq_f8": _nq_share(("random", 21, 250, 2, 3), 8, N=12, chunk=32, floor=128,
+                             capacity=1 << 14),
+    # the root alone: the whole tree against the frozen sequential counts
+    "root_nq_f-1": _nq_share(("root",), -1, N=10, m=1, chunk=64, floor=64, capacity=1 << 14,
+                             whole_tree=(35538, 724)),
+    "root_nq_f3": _nq_share(("root",), 3, N=10, m=1, chunk=64, floor=64, capacity=1 << 14,
+                            whole_tree=(35538, 724)),
+    "root_nq_f8": _nq_share(("root",), 8, N=12, m=1, chunk=16, floor=64, capacity=1 << 14,
+                            whole_tree=(856188, 14200)),
+}
+SHARE_CASES.update({
+    # two thieves served by successive donations, one of which donates itself
+    "three_nq": _nq_share(("root",), 3, N=11, m=1, chunk=128, floor=64, capacity=1 << 14, threads=3,
+                          need=dict(taken=2, thieves=2, at_floor=2), whole_tree=(166925, 2680)),
+    # the real floor at its edge: 65536 nodes at the first readback, by
+    # arithmetic (leaf parents lose exactly `chunk` nodes per iteration)
+    "edge_nq": _nq_share(("leaves", REAL_FLOOR + BATCH * 64), 8, N=10, chunk=64,
+                         capacity=1 << 17, need=dict(taken=1, at_floor=1)),
+    "below_edge_nq": _nq_share(("leaves", REAL_FLOOR + BATCH * 64 - 1), 8, N=10, chunk=64,
+                               capacity=1 << 17, need={}),
+    # the real floor with work in the donated half (depth >= N - 3)
+    "deep_nq": _nq_share(("random", 22, 100000, 9, 12), 8, N=12, chunk=256, capacity=1 << 17,
+                         need=dict(taken=1, at_floor=1)),
+    # m > floor / 2: the 2m branch decides (81920 >= 65536 would donate)
+    "two_m_nq": _nq_share(("leaves", 2 * 40000 + BATCH * 64), 8, N=10, m=40000, chunk=64,
+                          capacity=1 << 17, need=dict(taken=1, at_floor=1)),
+    "below_two_m_nq": _nq_share(("leaves", 2 * 40000 + BATCH * 64 - 1), 8, N=10, m=40000,
+                                chunk=64, capacity=1 << 17, need={}),
+    # a donation next to spills (spill_nq's capacity; the front half of its
+    # pool, then 400 leaf parents). The first readback (one iteration, 64 leaf
+    # parents popped: 736 nodes) donates the 368 at the back, leaf parents
+    # mostly, so the thief is soon waiting again; the donor keeps 368 > 900 -
+    # 640 nodes and spills next, and its drained runs start with 184 or more
+    # nodes >= the floor and find the thief waiting: a thread stays a runner
+    # between its run_pool calls, or that thief would have left
+    "spill_nq": _nq_share(("bfs+leaves", 4096, 0, 400, 400), -1, N=10, chunk=64, capacity=900,
+                          floor=64, need=dict(taken=2, spills=2, drained_donations=1, at_floor=1)),
+    # lb1_d with the incumbent fixed at the optimum (order-free counts) ...
+    "lb1_d": ShareCase("pfsp", ("bfs", 4096, 1040, 1100), inst=14, lb="lb1_d", chunk=32,
+                       capacity=1 << 12, floor=64, need=dict(taken=1, at_floor=1)),
+    # ... and starting 60 above it: the incumbent moves, the records are checked
+    # (frontier node 2987 holds the optimum 1377; the tail of leaf parents
+    # lowers the incumbent to 1398 in the first iteration, so the first offer
+    # already carries a better value than the run started from)
+    "lb1_d_open": ShareCase("pfsp", ("bfs+good", 4096, 2984, 2990), inst=14, lb="lb1_d", m=5,
+                            chunk=64, capacity=1 << 13, floor=64, best_delta=60, fixed_best=False,
+                            need=dict(taken=1, at_floor=1)),
+    # the S = 4 configuration: lb2 on a 20x10 instance, four threads
+    "lb2_four": ShareCase("pfsp", ("bfs", 4096, 1000, 1150), inst=14, lb="lb2", chunk=32,
+                          capacity=1 << 13, floor=64, threads=4,
+                          need=dict(taken=2, thieves=2, at_floor=2)),
+    # no donation wanted: the pool stays far below the real floor
+    "small_nq": _nq_share(("bfs", 25), 2, N=10, chunk=4096, capacity=1 << 17, need={},
+                          whole_tree=(35538, 724)),
+    # one batch, then leftovers; the thief finds no runner or nothing to take
+    "one_batch_nq": _nq_share(("bfs", 6000), 4, N=12, chunk=128, max_batches=1, need={}),
+})
+
+
+def share_case_pool(core, c):
+    """(pool bytes, tree, sol counted before the pool)."""
+    import devpool_step_oracle as orc
+    kind = c.pool[0]
+    if kind == "bfs":
+        return case_pool(core, c)
+    if kind == "bfs+good":
+        pool, t, s = case_pool(core, c)
+        return pool + orc.random_pfsp_nodes(orc.rng(c.inst), 63, min_depth=19) + \
+            orc.pfsp_node(19, orc.GOOD_PERM[c.inst]), t, s
+    if kind == "root":
+        return orc.nq_node(0, range(c.N)), 0, 0
+    if kind == "bfs+leaves":
+        pool, t, s = core.nq_bfs_frontier(c.N, 1, c.pool[1])
+        pool = pool[c.pool[2] * NODE:c.pool[3] * NODE]
+        return pool + orc.random_nq_nodes(orc.rng(5), c.pool[4], c.N, c.N, c.N), t, s
+    if kind == "leaves":
+        return orc.random_nq_nodes(orc.rng(c.pool[1]), 64, c.N, c.N, c.N) * (c.pool[1] // 64) + \
+            orc.random_nq_nodes(orc.rng(7), c.pool[1] % 64, c.N, c.N, c.N), 0, 0
+    _, seed, n, lo, hi = c.pool
+    return orc.random_nq_nodes(orc.rng(seed), n, c.N, lo, hi), 0, 0
+
+
+def share_case_model(core, c):
+    """The one-thread model of the case (no donation): where the pool stands at
+    each readback."""
+    pool, _, _ = share_case_pool(core, c)
+    best = case_best(core, c)
+    return loop_model(case_step_fn(core, c), pool, c.cfg(), best + c.best_delta)
+
+
+def at_floor(out, floor):
+    return sum(r["ctl"]["size"] >= floor for r in batches_of(out["trace"]))
+
+
+def run_share_case(core, c, pool):
+    if c.problem == "nq":
+        return core.nq_devpool_share(pool, c.N, 1, c.finish, c.m, c.chunk, c.capacity,
+                                     c.max_batches, c.threads, c.floor, c.await_ms)
+    best = case_best(core, c) + c.best_delta
+    return core.pfsp_devpool_share(pool, c.inst, c.lb, best, c.m, c.chunk, c.capacity,
+                                   c.max_batches, c.br, c.threads, c.floor, c.await_ms)

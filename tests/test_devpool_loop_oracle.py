@@ -9,7 +9,13 @@
     reaches the path);
   * the checkers raise on each single corruption of a correct trace;
   * nq_devpool_loop / pfsp_devpool_loop reject malformed input on the host,
-    before the first HIP call (no GPU needed)."""
+    before the first HIP call (no GPU needed);
+  * the same for the share runs (several slice threads over one SliceShare,
+    tests/test_gpu_devpool_share.py): every pool reaches its donation floor on
+    the one-thread model with a factor 2 of slack (or, at the real floor's
+    edge, by arithmetic), check_share accepts a consistent set of traces and
+    raises on each single corruption, and nq_devpool_share /
+    pfsp_devpool_share validate on the host."""
 import os
 import sys
 
@@ -361,3 +367,310 @@ def test_lb12_nodes_with_jobs_at_the_back_need_their_rule(core):
     assert any(pool[i + 22] for i in range(0, len(pool), NODE))
     with pytest.raises(ValueError):
         core.pfsp_devpool_loop(pool, 14, "lb12", 1377, capacity=4096, max_batches=1)
+
+
+# ---------------------------------------------------------------------------
+# share runs: helpers/devpool_loop_oracle.py's SHARE_CASES and check_share
+# ---------------------------------------------------------------------------
+
+_share = {}
+
+
+def share(core, name):
+    """(case, pool, bfs tree, bfs sol, seq, one-thread model): computed once."""
+    if name not in _share:
+        c = orc.SHARE_CASES[name]
+        pool, t0, s0 = orc.share_case_pool(core, c)
+        _share[name] = (c, pool, t0, s0, orc.case_seq(core, c), orc.share_case_model(core, c))
+    return _share[name]
+
+
+@pytest.mark.parametrize("name", sorted(orc.SHARE_CASES))
+def test_share_pool_reaches_its_floor_on_the_model(core, name):
+    c, pool, t0, s0, seq, out = share(core, name)
+    floor = c.floor_in_force()
+    n = orc.at_floor(out, floor)
+    print(name, "floor", floor, "readbacks at or above it", n, "of", len(orc.batches_of(out["trace"])))
+    if c.floor == 0 and c.need.get("at_floor") and c.pool[0] == "leaves":
+        assert n == 1                                  # the edge: exactly one, by arithmetic
+    elif c.need.get("at_floor"):
+        assert n >= 2 * c.need["at_floor"], (n, c.need)
+    else:
+        assert n == 0, "a case without a donation must stay below the floor"
+    if c.whole_tree is not None:
+        assert (t0 + out["tree"], s0 + out["sol"]) == c.whole_tree
+    if c.problem == "pfsp":
+        assert out["best"] == core.taillard_best_ub(c.inst)
+
+
+@pytest.mark.parametrize("name, floor", [("edge_nq", 1 << 16), ("below_edge_nq", 1 << 16),
+                                         ("two_m_nq", 80000), ("below_two_m_nq", 80000)])
+def test_real_floor_edge_by_arithmetic(core, name, floor):
+    c, pool, _, _, _, out = share(core, name)
+    cfg, n0 = c.cfg(), len(pool) // NODE
+    assert c.floor == 0 and cfg.floor == floor == core.donation_floor(c.m)
+    b = orc.batch_len(cfg, n0, 0)                      # derived, not assumed
+    assert b == orc.BATCH
+    # leaf parents push nothing: every iteration loses exactly `chunk` nodes
+    assert all(pool[i] == c.N for i in range(0, len(pool), NODE))
+    edge = name in ("edge_nq", "two_m_nq")
+    first = n0 - b * c.chunk
+    assert first == (floor if edge else floor - 1)
+    sizes = [r["ctl"]["size"] for r in orc.batches_of(out["trace"])]
+    assert sizes[0] == first and all(s < floor for s in sizes[1:])
+    # after the one donation of floor // 2 nodes neither half reaches the floor again
+    assert first - first // 2 < floor
+    if edge:
+        assert first // 2 == floor // 2
+    if name.endswith("two_m_nq"):
+        assert floor == 2 * c.m > (1 << 16) and first >= (1 << 16)  # the 2m branch decides
+
+
+def share_traces(core, name, threads=2):
+    c, pool, _, _, seq, _ = share(core, name)
+    key = (name, threads)
+    if key not in _share:
+        best = orc.case_best(core, c)
+        _share[key] = orc.share_model(orc.case_step_fn(core, c), pool, c.cfg(), best, threads)
+    return c, pool, seq, _share[key]
+
+
+def copies(outs):
+    return [copy_of(o) for o in outs]
+
+
+def find(out, kind, k=0):
+    return [i for i, r in enumerate(out["trace"]) if r["kind"] == kind][k]
+
+
+@pytest.mark.parametrize("name, threads", [("mixed_nq_f-1", 2), ("mixed_nq_f3", 3),
+                                           ("spill_nq", 2), ("lb1_d", 2), ("lb1_d", 4),
+                                           ("root_nq_f3", 2)])
+def test_check_share_accepts_a_consistent_set_of_traces(core, name, threads):
+    c, pool, seq, outs = share_traces(core, name, threads)
+    n = orc.share_counts(outs)
+    # every thread donates once while its pool reaches the floor: lb1_d's third
+    # half does not, and its fourth thread stays idle
+    want = 2 if (name, threads) == ("lb1_d", 4) else threads - 1
+    assert n["taken"] == n["takes"] == want and n["chains"] == want - 1, n
+    assert n["idle_threads"] == threads - 1 - want
+    total = orc.check_share(outs, pool, seq, c.cfg())
+    assert total == seq(pool)
+    # symmetric in the threads
+    orc.check_share(outs[::-1], pool, seq, c.cfg())
+    # and without the counts
+    orc.check_share(outs, pool, None, c.cfg())
+
+
+SHARE_BITES = ["mixed_nq_f-1", "lb1_d"]
+
+
+@pytest.mark.parametrize("name", SHARE_BITES)
+@pytest.mark.parametrize("what", ["dropped", "duplicated"])
+@pytest.mark.parametrize("side", ["take", "both"])
+def test_share_raises_on_one_donated_node_dropped_or_duplicated(core, name, what, side):
+    c, pool, seq, good = share_traces(core, name)
+    outs = copies(good)
+    d = outs[0]["trace"][find(outs[0], "donate")]
+    t = outs[1]["trace"][find(outs[1], "take")]
+    run = outs[1]["trace"][find(outs[1], "run")]
+    nodes = t["nodes"]
+    i = (len(nodes) // NODE) // 2
+    assert nodes[i * NODE:(i + 1) * NODE] != nodes[(i + 1) * NODE:(i + 2) * NODE]
+    if what == "dropped":
+        nodes = nodes[:i * NODE] + nodes[(i + 1) * NODE:]
+        t["size"] -= 1
+        run["init_size"] -= 1
+    else:
+        nodes = nodes[:(i + 1) * NODE] + nodes[i * NODE:(i + 1) * NODE] + nodes[(i + 2) * NODE:]
+    t["nodes"] = nodes
+    if side == "both":
+        d["moved"] = nodes
+    with pytest.raises(AssertionError):
+        orc.check_share(outs, pool, seq, c.cfg())
+    with pytest.raises(AssertionError):
+        orc.check_share(outs, pool, None, c.cfg())
+
+
+@pytest.mark.parametrize("name", SHARE_BITES)
+def test_share_raises_on_the_front_half_donated(core, name):
+    c, pool, seq, good = share_traces(core, name)
+    outs = copies(good)
+    i = find(outs[0], "donate")
+    d, prev = outs[0]["trace"][i], outs[0]["trace"][i - 1]
+    half = d["size_before"] // 2
+    front = prev["pool"][:half * NODE]
+    assert prev["kind"] == "batch" and front != d["moved"]
+    d["moved"] = front
+    outs[1]["trace"][find(outs[1], "take")]["nodes"] = front
+    with pytest.raises(AssertionError, match="back half"):
+        orc.check_share(outs, pool, None, c.cfg())
+
+
+@pytest.mark.parametrize("name", SHARE_BITES)
+@pytest.mark.parametrize("off", [-1, 1])
+def test_share_raises_on_size_after_off_by_one(core, name, off):
+    c, pool, seq, good = share_traces(core, name)
+    outs = copies(good)
+    outs[0]["trace"][find(outs[0], "donate")]["size_after"] += off
+    with pytest.raises(AssertionError):
+        orc.check_share(outs, pool, None, c.cfg())
+    # ... also when the next batch agrees with the wrong size
+    outs[0]["trace"][find(outs[0], "donate") + 1]["size_before"] += off
+    with pytest.raises(AssertionError):
+        orc.check_share(outs, pool, None, c.cfg())
+
+
+@pytest.mark.parametrize("name", SHARE_BITES)
+def test_share_raises_on_a_take_with_one_byte_changed(core, name):
+    c, pool, seq, good = share_traces(core, name)
+    outs = copies(good)
+    t = outs[1]["trace"][find(outs[1], "take")]
+    b = bytearray(t["nodes"])
+    b[len(b) // 2] ^= 1
+    t["nodes"] = bytes(b)
+    with pytest.raises(AssertionError):
+        orc.check_share(outs, pool, None, c.cfg())
+
+
+def test_share_raises_on_a_thief_starting_above_the_offered_incumbent(core):
+    c, pool, seq, good = share_traces(core, "lb1_d")
+    outs = copies(good)
+    t = outs[1]["trace"][find(outs[1], "take")]
+    run = outs[1]["trace"][find(outs[1], "run")]
+    assert run["best"] == t["best"]
+    run["best"] += 1
+    with pytest.raises(AssertionError, match="starts above the offer"):
+        orc.check_share(outs, pool, seq, c.cfg())
+    run["best"] -= 2  # a lower shared incumbent is fine
+    orc.check_share(outs, pool, None, c.cfg())
+
+
+def test_share_raises_on_a_wrong_offered_incumbent(core):
+    c, pool, seq, good = share_traces(core, "lb1_d")
+    outs = copies(good)
+    outs[0]["trace"][find(outs[0], "donate")]["best"] += 1
+    outs[1]["trace"][find(outs[1], "take")]["best"] += 1
+    with pytest.raises(AssertionError, match="offered incumbent"):
+        orc.check_share(outs, pool, None, c.cfg())
+
+
+@pytest.mark.parametrize("name", SHARE_BITES)
+def test_share_raises_on_a_donation_below_the_floor(core, name):
+    c, pool, seq, good = share_traces(core, name)
+    d = good[0]["trace"][find(good[0], "donate")]
+    cfg = c.cfg()
+    cfg.floor = d["size_before"]
+    orc.check_share(good, pool, None, cfg)
+    cfg.floor = d["size_before"] + 1
+    with pytest.raises(AssertionError, match="below the floor"):
+        orc.check_share(good, pool, None, cfg)
+
+
+@pytest.mark.parametrize("name", SHARE_BITES)
+def test_share_raises_on_a_stale_prefix_after_a_donation(core, name):
+    c, pool, seq, good = share_traces(core, name)
+    i = find(good[0], "donate")
+    d, nxt = good[0]["trace"][i], good[0]["trace"][i + 1]
+    keep = (d["size_after"] - nxt["b"] * c.chunk) * NODE
+    assert nxt["kind"] == "batch" and keep > NODE
+    # one byte of the kept front changed
+    outs = copies(good)
+    b = bytearray(nxt["pool"])
+    b[keep - NODE + 1] ^= 1
+    outs[0]["trace"][i + 1]["pool"] = bytes(b)
+    with pytest.raises(AssertionError, match="un-popped prefix"):
+        orc.check_share(outs, pool, None, c.cfg())
+    # the donor went on with the size it had before the donation
+    outs = copies(good)
+    outs[0]["trace"][i + 1]["size_before"] = d["size_before"]
+    with pytest.raises(AssertionError):
+        orc.check_share(outs, pool, None, c.cfg())
+
+
+def test_share_raises_on_unmatched_takes_and_offers(core):
+    c, pool, seq, good = share_traces(core, "mixed_nq_f-1")
+    # a take without a donation: the donor's record gone, its sizes patched up
+    outs = copies(good)
+    del outs[0]["trace"][find(outs[0], "donate")]
+    with pytest.raises(AssertionError):
+        orc.check_share(outs, pool, None, c.cfg())
+    # a taken offer nobody received
+    outs = copies(good)
+    outs[1] = dict(outs[1], trace=[], leftover=b"", tree=0, sol=0, iters=0,
+                   diag=dict.fromkeys(outs[1]["diag"], 0))
+    with pytest.raises(AssertionError, match="no other thread received"):
+        orc.check_share(outs, pool, None, c.cfg())
+    # the thief is the donor itself
+    outs = copies(good)
+    outs[0]["trace"] = outs[0]["trace"] + outs[1]["trace"]
+    outs[1]["trace"] = []
+    with pytest.raises(AssertionError):
+        orc.check_share(outs, pool, None, c.cfg())
+
+
+def test_share_withdrawn_offer_keeps_the_pool(core):
+    c, pool, seq, good = share_traces(core, "mixed_nq_f-1")
+    # the one-thread model with a withdrawn offer after its first readback at the floor
+    one = copy_of(share(core, "mixed_nq_f-1")[5])
+    i = next(i for i, r in enumerate(one["trace"])
+             if r["kind"] == "batch" and r["ctl"]["size"] >= c.floor_in_force())
+    r = one["trace"][i]
+    size = r["ctl"]["size"]
+    moved = r["pool"][(size - size // 2) * NODE:]
+    one["trace"].insert(i + 1, dict(kind="donate", size_before=size, size_after=size, moved=moved,
+                                    best=r["ctl"]["best"], taken=False, withdrawn=True))
+    idle = dict(good[1], trace=[], leftover=b"", tree=0, sol=0, iters=0,
+                diag=dict.fromkeys(good[1]["diag"], 0))
+    orc.check_share([one, idle], pool, seq, c.cfg())
+    assert orc.share_counts([one, idle])["withdrawn"] == 1
+    # withdrawn, yet the size shrank
+    bad = copy_of(one)
+    bad["trace"][i + 1]["size_after"] = size - size // 2
+    with pytest.raises(AssertionError):
+        orc.check_share([bad, idle], pool, None, c.cfg())
+
+
+def test_share_global_conservation_bites(core):
+    c, pool, seq, good = share_traces(core, "mixed_nq_f-1")
+    outs = copies(good)
+    outs[1]["tree"] += 1
+    with pytest.raises(AssertionError):
+        orc.check_share(outs, pool, seq, c.cfg())
+
+
+@pytest.mark.parametrize("kwargs", [
+    dict(threads=1), dict(threads=5), dict(threads=0), dict(threads=-2),
+    dict(donate_floor=1), dict(donate_floor=-1), dict(donate_floor=-64),
+    dict(await_idle_ms=-1), dict(await_idle_ms=5001),
+    dict(nodes=b""), dict(nodes=NQ_OK[:23]), dict(N=3),
+    dict(nodes=step.nq_node(2, [1, 1, 0, 2, 4, 5])),
+    dict(m=0), dict(chunk=0), dict(chunk=65, capacity=64),
+    dict(capacity=(1 << 22) + 1),                      # the per-thread trace bound
+    dict(max_batches=-1), dict(max_batches=4097), dict(finish=9),
+])
+def test_nq_share_rejects_malformed_input(core, kwargs):
+    args = dict(nodes=NQ_OK, N=6, chunk=8, capacity=64, max_batches=2, threads=2,
+                donate_floor=2, await_idle_ms=10)
+    args.update(kwargs)
+    with pytest.raises(ValueError):
+        core.nq_devpool_share(**args)
+
+
+@pytest.mark.parametrize("kwargs", [
+    dict(threads=1), dict(threads=5),
+    dict(donate_floor=1), dict(donate_floor=-1),
+    dict(await_idle_ms=-1), dict(await_idle_ms=5001),
+    dict(nodes=b""), dict(nodes=PF_OK + b"\0"),
+    dict(nodes=_pf(3, [0] + list(range(19)))),
+    dict(m=0), dict(chunk=0), dict(chunk=65, capacity=64),
+    dict(capacity=(1 << 22) + 1),
+    dict(max_batches=4097), dict(best=0), dict(lb="bogus"), dict(br="sideways"),
+    dict(lb="lb2", br="bwd"), dict(inst=31),
+])
+def test_pfsp_share_rejects_malformed_input(core, kwargs):
+    args = dict(nodes=PF_OK, inst=2, lb="lb1", best=1359, chunk=8, capacity=64, max_batches=2,
+                threads=2, donate_floor=2, await_idle_ms=10)
+    args.update(kwargs)
+    with pytest.raises(ValueError):
+        core.pfsp_devpool_share(**args)
