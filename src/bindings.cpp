@@ -7,6 +7,7 @@
 #include <cstring>
 #include <stdexcept>
 
+#include "devpool_loop_plan.hpp"
 #include "engine_gpu.hpp"
 #include "gpu_api.hpp"
 #include "nodes.hpp"
@@ -970,6 +971,34 @@ PYBIND11_MODULE(_core, mod) {
           py::arg("device") = 0);
 
   mod.def("pool_selftest", &pool_selftest);
+  // The loop driver's planner (devpool_loop_plan.hpp), read-only; no GPU needed.
+  mod.attr("LOOP_BATCH") = LOOP_BATCH;
+  mod.attr("LOOP_EAGER_BATCHES") = LOOP_EAGER_BATCHES;
+  mod.attr("LOOP_SMALL_POOL") = LOOP_SMALL_POOL;
+  mod.def(
+      "devpool_plan_batch",
+      [](unsigned long long m, int per, unsigned long long growth, unsigned long long capacity,
+         unsigned long long stop_size, unsigned long long size, int batches,
+         bool can_spill) -> py::object {
+        DevLoopShape c;
+        c.m = m;
+        c.per = per;
+        c.growth = growth;
+        c.capacity = capacity;
+        c.stop_size = stop_size;
+        const int b = plan_batch(c, size, batches, can_spill);
+        return b ? py::object(py::int_(b)) : py::object(py::str("spill"));
+      },
+      py::arg("m"), py::arg("per"), py::arg("growth"), py::arg("capacity"),
+      py::arg("stop_size"), py::arg("size"), py::arg("batches"), py::arg("can_spill"));
+  mod.def(
+      "devpool_plan_graph",
+      [](bool allowed, int batches, bool have_exec, int b, int par) {
+        static const char* names[] = {"eager", "capture", "replay"};
+        return names[static_cast<int>(plan_graph(allowed, batches, have_exec, b, par))];
+      },
+      py::arg("allowed"), py::arg("batches"), py::arg("have_exec"), py::arg("b"),
+      py::arg("par"));
   mod.def("donation_floor", &donation_floor, py::arg("m"));
   mod.def("share_selftest", &share_selftest, py::arg("scenario"), py::arg("size") = 0,
           py::arg("floor") = 0, py::arg("thieves") = 1, py::arg("offers") = 1,

@@ -32,6 +32,7 @@
 #include <string>
 #include <vector>
 
+#include "devpool_driver.hpp"
 #include "engine_gpu.hpp"
 #include "engine_internal.hpp"
 #include "gpu_api.hpp"
@@ -355,243 +356,6 @@ PfspPackedTables build_packed_johnson(const PfspInstance& I) {
   return pk;
 }
 
-// Shared devpool driver: capture BATCH iterations into a hipGraph once, then
-// replay + poll the 48 B control block until the pool drops below m
-// (graph replay ~10-16 us vs ~3.5 us host cost PER LAUNCH eager — the hot
-// loop is launch-bound at chunk sizes this small).
-// `shared_best` (optional): a cross-thread incumbent. Each readback publishes
-// the engine's best into it (atomic min) and adopts a lower value published by
-// other ranks/threads by writing ctl->best on the (synchronized) stream —
-// the RCCL incumbent-UB exchange of the distributed tier plugs in here.
-// enqueue_iter(parity, chunk_bound): parity alternates 0/1 per iteration —
-// iteration i reads ctl[parity] and gather2 writes ctl[1-parity]; the loop
-// tracks the live parity so hooks and readbacks always touch the block the
-// last gather wrote. chunk_bound is an upper bound on the pool size at that
-// iteration (exact at readbacks, x branching per blind iteration) so the
-// callee can size its launch grids to work that can actually exist; pop
-// semantics are unchanged because bound >= size implies
-// min(size, min(Mc, bound)) == min(size, Mc).
-// `readback_hook(host_ctl, live_ctl_d)`: called after every batch readback
-// with the stream idle; may reduce host_ctl->size after carving the pool (the
-// donor path of SliceShare) — it must then also write the device ctl itself.
-// `spill_hook(host_ctl, live_ctl_d)`: called (stream idle) when the next
-// iteration's worst-case growth no longer fits `capacity`; carves part of the
-// pool to host storage and rewrites both sizes. The caller re-runs spilled
-// nodes after the loop, so counts stay exact (Pool.chpl:28-31's unbounded-
-// growth contract, met by spilling instead of growing).
-using ReadbackHook = std::function<void(DevCtl*, DevCtl*)>;
-
-struct DevLoopCfg {
-  unsigned long long m = 1;          // loop exits when size < m
-  unsigned long long init_size = 0;  // pool size at entry
-  unsigned long long growth = 0;     // worst-case net pool growth per iteration
-  unsigned long long capacity = 0;   // pool capacity in nodes
-  unsigned long long stop_size = 0;  // frontier builder: stop once size >= this
-  int kernels_per_iter = 2;
-  int per = 1;                       // max children per node (grid-bound growth)
-  bool allow_graph = true;
-  int max_batches = 0;            // tests: end the loop after this many batches (0 = never)
-  DevLoopTrace* trace = nullptr;  // tests: one record per loop turn (engine_gpu.hpp)
-};
-
-static DevpoolStepCtl step_ctl_of(const DevCtl& c) {
-  return {c.size, c.chunk, c.tree, c.sol, c.iters, c.best, c.overflow};
-}
-
-constexpr unsigned long long LOOP_TRACE_MAX_NODES = 1ull << 22;
-
-// Copy `n` nodes into a trace record: from device memory over the (idle)
-// stream `s`, or from host memory when `on_device` is false.
-static void trace_nodes(DevLoopTrace& t, DevLoopRec& rec, const void* src,
-                        unsigned long long n, bool on_device, hipStream_t s) {
-  t.traced_nodes += n;
-  if (t.traced_nodes > LOOP_TRACE_MAX_NODES)
-    throw std::runtime_error("devpool loop trace exceeds 2^22 nodes");
-  rec.nodes.resize(n * t.node_bytes);
-  if (n == 0) return;
-  if (!on_device) {
-    std::memcpy(rec.nodes.data(), src, rec.nodes.size());
-    return;
-  }
-  HIP_CHECK(hipMemcpyAsync(rec.nodes.data(), src, rec.nodes.size(), hipMemcpyDeviceToHost, s));
-  HIP_CHECK(hipStreamSynchronize(s));
-}
-
-template <class EnqueueIter>
-static DevCtl run_devpool_loop(hipStream_t s, DevCtl* ctl_d, const DevLoopCfg& cfg,
-                               EnqueueIter&& enqueue_iter, Result& r,
-                               std::atomic<int>* shared_best = nullptr,
-                               const ReadbackHook& readback_hook = {},
-                               const ReadbackHook& spill_hook = {}) {
-  PinnedGuard<DevCtl> ctl_h(1);
-  const int BATCH = 16;
-  // GATS_NO_GRAPH=1 falls back to eager launches (rocprofv3 crashes tracing
-  // hipGraph replays on ROCm 7.2; eager mode gives identical results).
-  // Graph capture is LAZY: instantiation costs a few ms, which dominates
-  // small searches (PFSP ta0xx finish in <10 ms), so the first EAGER_BATCHES
-  // batches run eager and the graph is built only if the search is still
-  // going.
-  // multi-slice engines pass allow_graph=false: ROCm 7.2 stream capture races
-  // with concurrent async work from the other slice threads no matter the
-  // capture mode; with >1 slice in flight the host launch latency is hidden
-  // by the other slices anyway
-  const bool graph_allowed = cfg.allow_graph && cfg.stop_size == 0 &&
-                             std::getenv("GATS_NO_GRAPH") == nullptr;
-  const int EAGER_BATCHES = 4;
-  int batches = 0;
-  int par = 0;  // parity of the NEXT iteration == index of the live ctl block
-  unsigned long long last_size = cfg.init_size;
-  // chunk BOUND handed to each launch so its grid covers only the pool that
-  // can possibly exist: exact at readbacks, multiplied by the branching
-  // factor per blind iteration. Full-size grids for tiny chunks were the
-  // small-search floor (an 80-node ta019 tree dispatched 15k-block lb2
-  // grids: 1.53 ms; the engine infra itself costs 0.025 ms).
-  hipGraph_t graph = nullptr;
-  hipGraphExec_t exec = nullptr;
-  bool overflow = false;
-  *ctl_h.p = DevCtl{};
-  ctl_h.p->size = cfg.init_size;
-  while (true) {
-    // capacity-aware batch: never launch more iterations than worst-case
-    // growth allows; spill when even one iteration might not fit. Small
-    // pools use short batches so the chunk bound (and with it the launch
-    // grids) is re-tightened every couple of iterations.
-    int b = (cfg.stop_size > 0) ? 1 : BATCH;
-    if (cfg.per > 1 && last_size < 4096 && b > 2) b = 2;
-    if (cfg.growth > 0 && cfg.capacity > 0) {
-      const unsigned long long room =
-          cfg.capacity > last_size ? cfg.capacity - last_size : 0;
-      const unsigned long long bmax = room / cfg.growth;
-      if (bmax == 0 && spill_hook && last_size >= 4 * cfg.m && batches > 0) {
-        if (cfg.trace) {
-          cfg.trace->recs.emplace_back();
-          cfg.trace->recs.back().kind = DevLoopRec::SPILL;
-          cfg.trace->recs.back().size_before = last_size;
-        }
-        spill_hook(ctl_h.p, ctl_d + par);  // fills the record's nodes
-        last_size = ctl_h.p->size;
-        if (cfg.trace) cfg.trace->recs.back().size_after = last_size;
-        continue;
-      }
-      if (bmax == 0) {
-        // worst-case doesn't fit but the actual child count usually does;
-        // run one iteration — the gather kernel's exact-fit guard flags a
-        // REAL overflow, which is fatal (the iteration state is torn)
-        b = 1;
-      } else if (bmax < static_cast<unsigned long long>(b)) {
-        b = static_cast<int>(bmax);
-      }
-    }
-    bool captured = false;
-    const int par_in = par;
-    if (graph_allowed && batches >= EAGER_BATCHES && exec == nullptr && b == BATCH &&
-        par == 0) {
-      // one capture at a time: concurrent captures from the slice threads
-      // race inside ROCm 7.2 ("previous error during capture"); relaxed mode
-      // lets the other slices keep launching meanwhile. A failed capture is
-      // not fatal — the loop just stays eager.
-      static std::mutex capture_mu;
-      std::lock_guard<std::mutex> lock(capture_mu);
-      hipError_t ce = hipStreamBeginCapture(s, hipStreamCaptureModeRelaxed);
-      if (ce == hipSuccess) {
-        for (int i = 0; i < BATCH; i++) enqueue_iter(i & 1, ~0ull);
-        ce = hipStreamEndCapture(s, &graph);
-        if (ce == hipSuccess) {
-          if (hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0) != hipSuccess) {
-            (void)hipGraphDestroy(graph);
-            graph = nullptr;
-            exec = nullptr;
-          }
-        } else {
-          graph = nullptr;
-        }
-        // a successfully captured batch was not EXECUTED; replay it below or
-        // re-run eagerly — either way the work happens exactly once
-        if (exec == nullptr) (void)hipGetLastError();
-        captured = exec != nullptr;
-      } else {
-        (void)hipGetLastError();
-      }
-    }
-    const bool replay = exec != nullptr && b == BATCH && par == 0;
-    if (replay) {
-      HIP_CHECK(hipGraphLaunch(exec, s));  // even count: parity unchanged
-    } else {
-      unsigned long long bound = last_size ? last_size : 1;
-      for (int i = 0; i < b; i++) {
-        enqueue_iter(par, bound);
-        par ^= 1;
-        if (bound < (1ull << 40)) bound *= cfg.per > 1 ? cfg.per : 2;
-      }
-    }
-    batches++;
-    HIP_CHECK(
-        hipMemcpyAsync(ctl_h.p, ctl_d + par, sizeof(DevCtl), hipMemcpyDeviceToHost, s));
-    HIP_CHECK(hipStreamSynchronize(s));
-    r.kernel_launch += static_cast<uint64_t>(cfg.kernels_per_iter) * b;
-    r.d2h++;
-    r.d2h_bytes += sizeof(DevCtl);
-    static const bool chk = std::getenv("GATS_DEVPOOL_CHECK") != nullptr;
-    if (chk && cfg.growth > 0 &&
-        ctl_h.p->size > last_size + static_cast<unsigned long long>(b) * cfg.growth)
-      fprintf(stderr, "DEVPOOL VIOLATION: size %llu -> %llu after %d iters (growth %llu)\n",
-              last_size, ctl_h.p->size, b, cfg.growth);
-    if (cfg.trace) {
-      DevLoopTrace& t = *cfg.trace;
-      t.recs.emplace_back();
-      DevLoopRec& rec = t.recs.back();
-      rec.kind = DevLoopRec::BATCH;
-      rec.b = b;
-      rec.parity = par_in;
-      rec.graph = replay;
-      rec.captured = captured;
-      rec.size_before = last_size;
-      rec.ctl = step_ctl_of(*ctl_h.p);
-      if (!ctl_h.p->overflow) {
-        if (ctl_h.p->size > cfg.capacity)
-          throw std::runtime_error("devpool loop: size exceeds capacity");
-        trace_nodes(t, rec, t.pool_d, ctl_h.p->size, /*on_device=*/true, s);
-      }
-    }
-    last_size = ctl_h.p->size;
-    if (ctl_h.p->overflow) {
-      overflow = true;
-      break;
-    }
-    if (readback_hook) {
-      readback_hook(ctl_h.p, ctl_d + par);
-      last_size = ctl_h.p->size;
-    }
-    if (shared_best) {
-      int mine = ctl_h.p->best;
-      int cur = shared_best->load(std::memory_order_relaxed);
-      while (mine < cur && !shared_best->compare_exchange_weak(cur, mine,
-                                                               std::memory_order_relaxed)) {
-      }
-      cur = shared_best->load(std::memory_order_relaxed);
-      if (cur < mine) {
-        // adopt the lower incumbent; the stream is idle (synchronized above),
-        // so no device atomicMin can race this write
-        HIP_CHECK(hipMemcpyAsync(&(ctl_d + par)->best, &cur, sizeof(int),
-                                 hipMemcpyHostToDevice, s));
-        HIP_CHECK(hipStreamSynchronize(s));
-      }
-    }
-    if (cfg.stop_size > 0 && ctl_h.p->size >= cfg.stop_size) break;
-    if (ctl_h.p->size < cfg.m) break;
-    if (cfg.max_batches > 0 && batches >= cfg.max_batches) break;
-  }
-  if (exec != nullptr) {
-    (void)hipGraphExecDestroy(exec);
-    (void)hipGraphDestroy(graph);
-  }
-  if (overflow)
-    throw std::runtime_error(
-        "device pool overflow: capacity too small for one offload iteration even after "
-        "spilling; raise --capacity (or lower --M)");
-  return *ctl_h.p;
-}
-
 // ---------------------------------------------------------------------------
 // Multi-slice devpool: S independent device pools driven on S HIP streams by
 // S host threads — ONE devpool loop is a serial expand->gather dependency
@@ -599,8 +363,9 @@ static DevCtl run_devpool_loop(hipStream_t s, DevCtl* ctl_d, const DevLoopCfg& c
 // the wide-chunk change, filled the otherwise half-idle chip). The frontier
 // is round-robin split exactly like the multi-GPU partition
 // (nqueens_multigpu_chpl.chpl:221-226), just inside one device; a drained
-// thread takes donated half-pools (SliceShare below). Counts are
-// slice-order independent. S default: see devpool_slices().
+// thread takes donated half-pools (SliceShare). Counts are slice-order
+// independent. S default: see devpool_slices(). The loop
+// driver and the slice thread themselves are in devpool_driver.hpp.
 // ---------------------------------------------------------------------------
 
 // Concurrent slice chains per device. Wide-chunk paths (N-Queens, lb1,
@@ -617,293 +382,6 @@ static int devpool_slices(int lbk = 1) {
     return v < 1 ? 1 : v;
   }
   return (lbk == 2) ? 4 : 2;
-}
-
-// Internal per-iteration expansion width of the devpool. The reference's M
-// caps how many nodes are COPIED to the GPU per offload round
-// (pfsp_gpu_cuda.c:424-426); a device-resident pool has no copy window, so
-// the devpool widens the chunk to ~512k nodes — one launch then fills the
-// 256 CUs by itself and the iteration count drops ~10x. --M stays a lower
-// bound here (and is honored exactly in hostpool mode). Clamped so one
-// iteration's worst-case children still fit half the pool capacity (the
-// spill path needs that), and so chunk*branching fits u32 child indexing.
-static unsigned long long devpool_chunk_cap(int M, int per, unsigned long long capacity,
-                                            int lbk) {
-  // lb2's wave-cooperative kernel gives each CHILD a whole wave, so M=50000
-  // already launches ~16k waves (chip is full); widening it just multiplies
-  // the gather grid with empty slots and the worst-case growth bound
-  // (measured: spill storms + 687 us gathers on ta006 at a 419k chunk)
-  unsigned long long c = (lbk == 2) ? static_cast<unsigned long long>(M) : (1ull << 19);
-  if (const char* e = std::getenv("GATS_DEVPOOL_CHUNK")) c = strtoull(e, nullptr, 10);
-  const unsigned long long fit = capacity / (2 * static_cast<unsigned long long>(per));
-  if (c > fit) c = fit;
-  if (c < static_cast<unsigned long long>(M)) c = M;  // user window is the floor
-  const unsigned long long lim = (1ull << 31) / per;
-  if (c > lim) c = lim;
-  return c;
-}
-
-struct SliceOut {
-  DevCtl fin{};
-  Result diag;
-};
-
-// Work-sharing between the slice threads of ONE engine: a thread whose queue
-// drained waits here; a running thread donates the BACK half of its device
-// pool at a readback boundary (stream synced, so the handoff region is
-// quiescent until the thief's D2D copy acks). Steal-half + the >=2m donor
-// threshold mirror the reference's stealing rule (Pool_par.chpl:153-165);
-// all waits are bounded, and a waiter exits once no runner remains.
-// SliceShare, the floor and both sides of the handshake live in
-// slice_share.hpp (no HIP there); devpool_thread supplies the device actions.
-
-// What a slice thread's readback and spill hooks see: the host copy of the
-// live control block, its device address, the thread's pool and stream (idle
-// at that point) and the thread's counters.
-template <class NodeT>
-struct SliceReadback {
-  DevCtl* hc;
-  DevCtl* live;
-  const NodeT* pool_d;
-  hipStream_t s;
-  Result& r;
-};
-template <class NodeT>
-using SliceReadbackFn = std::function<void(const SliceReadback<NodeT>&)>;
-
-// MOVE the back half of the live pool to host memory: copy it to
-// dest(half), shrink the size in both copies of the control block, wait, and
-// count the transfer. `dest_mu`, when given, is held while dest() makes room
-// and the copy is enqueued.
-template <class NodeT, class Dest>
-static void carve_back_half(const SliceReadback<NodeT>& rb, std::mutex* dest_mu, Dest&& dest) {
-  const unsigned long long half = rb.hc->size / 2;
-  const unsigned long long newsize = rb.hc->size - half;
-  {
-    std::unique_lock<std::mutex> l;
-    if (dest_mu) l = std::unique_lock<std::mutex>(*dest_mu);
-    HIP_CHECK(hipMemcpyAsync(dest(half), rb.pool_d + newsize, half * sizeof(NodeT),
-                             hipMemcpyDeviceToHost, rb.s));
-  }
-  HIP_CHECK(hipMemcpyAsync(&rb.live->size, &newsize, sizeof(newsize), hipMemcpyHostToDevice,
-                           rb.s));
-  HIP_CHECK(hipStreamSynchronize(rb.s));
-  rb.hc->size = newsize;
-  rb.r.d2h++;
-  rb.r.d2h_bytes += half * sizeof(NodeT);
-}
-
-// What the loop-driver test entry points add to a slice thread: the chunk cap
-// taken as given, a batch limit per loop call and the trace sink (donations
-// and takes are recorded in it too). With a SliceShare: `donate_floor`
-// replaces donation_floor(m) (0 = the real floor), and at a readback whose
-// pool is at or above the floor the thread first waits at most
-// `await_idle_ms` until each of the `threads` threads of the share is either
-// running or waiting for work (await_idle), so that a search of a few
-// milliseconds donates for certain.
-struct DevpoolThreadTest {
-  unsigned long long chunk = 0;
-  int max_batches = 0;
-  DevLoopTrace* trace = nullptr;
-  unsigned long long donate_floor = 0;
-  int await_idle_ms = 0;
-  int threads = 1;
-};
-
-// Queue-driven slice thread: allocates its device buffers once, then keeps
-// claiming frontier slices from the shared index until none remain. Slices
-// are oversubscribed (~4 per thread) so a thread whose slice finishes early
-// just pulls the next one; once the queue is empty it takes donated
-// half-pools of same-device threads (SliceShare). `shared_best` (optional) is
-// the cross-thread incumbent handed to run_devpool_loop: without it nothing is
-// published or written to the device. `on_readback` (optional) runs after
-// the donation check at every readback boundary.
-template <class Problem>
-static SliceOut devpool_thread(const Problem& problem,
-                               const std::vector<std::vector<typename Problem::Node>>& slices,
-                               std::atomic<int>& next_slice, int best0, int m, int M,
-                               int device, unsigned long long capacity,
-                               std::atomic<int>* shared_best, bool allow_graph,
-                               SliceShare* share,
-                               std::vector<typename Problem::Node>& leftover,
-                               const SliceReadbackFn<typename Problem::Node>& on_readback,
-                               const DevpoolThreadTest* test = nullptr) {
-  using NodeT = typename Problem::Node;
-  set_device_cached(device);
-  const Problem P = problem.on_device(device);
-  StreamGuard stream;
-  SliceOut out;
-  out.fin.best = best0;
-  Result& r = out.diag;
-  const unsigned long long Mc =
-      test ? test->chunk : devpool_chunk_cap(M, P.per, capacity, P.lbg);
-  const bool presum = devpool_presum_alloc(devpool_grid(Mc, P.per, P.lbg), P.lbg);
-  const DevpoolBufs<NodeT> bufs(capacity, Mc, P.per, P.lbg, Problem::needs_be, presum);
-  DevLoopTrace* const trace = test ? test->trace : nullptr;
-  if (trace) {
-    trace->pool_d = bufs.pool.p;
-    trace->node_bytes = sizeof(NodeT);
-  }
-  std::vector<NodeT> spilled;  // capacity-pressure spill, re-run after the slice
-
-  auto iter = [&](int parity, unsigned long long bound) {
-    const DevIterPolicy it = devpool_iter_policy(Mc, bound, P.per, P.lbg, presum);
-    P.enqueue(bufs, bufs.ctl.p + parity, bufs.ctl.p + (1 - parity), m, it.Mi, it.ps, stream.s);
-  };
-  // Donor side of SliceShare: runs at readback boundaries (stream idle).
-  auto donate = [&](DevCtl* hc, DevCtl* live) {
-    static const bool off = std::getenv("GATS_NO_DONATE") != nullptr;  // bisect knob
-    if (off || !share) return;
-    const unsigned long long floor_sz =
-        (test && test->donate_floor) ? test->donate_floor : donation_floor(m);
-    if (test && test->await_idle_ms > 0 && !hc->overflow && hc->size >= floor_sz)
-      await_idle(*share, test->threads, test->await_idle_ms);
-    const unsigned long long before = hc->size;
-    bool traced = false;
-    // the stream is idle (caller synced), so rewriting the live size is safe
-    auto set_size = [&](unsigned long long x) {
-      HIP_CHECK(hipMemcpyAsync(&live->size, &x, sizeof(x), hipMemcpyHostToDevice, stream.s));
-      HIP_CHECK(hipStreamSynchronize(stream.s));
-      if (trace && x < before) {  // the carve: the offer is not published yet
-        trace->recs.emplace_back();
-        DevLoopRec& rec = trace->recs.back();
-        rec.kind = DevLoopRec::DONATE;
-        rec.size_before = before;
-        rec.best = hc->best;
-        traced = true;
-        trace_nodes(*trace, rec, bufs.pool.p + x, before - x, /*on_device=*/true, stream.s);
-      }
-    };
-    const Donation d = donate_if_wanted(share, hc->size, hc->best, hc->overflow != 0,
-                                        bufs.pool.p, floor_sz, set_size);
-    if (traced) {
-      trace->recs.back().size_after = hc->size;
-      trace->recs.back().outcome = static_cast<int>(d);
-    }
-  };
-  ReadbackHook hook = [&](DevCtl* hc, DevCtl* live) {
-    donate(hc, live);
-    if (on_readback) on_readback({hc, live, bufs.pool.p, stream.s, r});
-  };
-  ReadbackHook spill = [&](DevCtl* hc, DevCtl* live) {
-    if (hc->size / 2 == 0) return;
-    const size_t before = spilled.size();
-    carve_back_half<NodeT>({hc, live, bufs.pool.p, stream.s, r}, nullptr,
-                           [&](unsigned long long half) {
-                             spilled.resize(spilled.size() + half);
-                             return spilled.data() + (spilled.size() - half);
-                           });
-    if (trace) {
-      const unsigned long long half = spilled.size() - before;
-      trace_nodes(*trace, trace->recs.back(), spilled.data() + before, half,
-                  /*on_device=*/false, stream.s);
-    }
-  };
-
-  DevLoopCfg cfg;
-  cfg.m = m;
-  cfg.capacity = capacity;
-  cfg.growth = Mc * P.per;  // worst-case children/iter
-  cfg.per = P.per;
-  cfg.allow_graph = allow_graph;
-  if (test) {
-    cfg.max_batches = test->max_batches;
-    cfg.trace = trace;
-  }
-
-  auto run_pool = [&](unsigned long long init_size, int init_best, bool from_spill = false) {
-    size_t run_rec = 0;
-    if (trace) {
-      run_rec = trace->recs.size();
-      trace->recs.emplace_back();
-      trace->recs.back().kind = DevLoopRec::RUN;
-      trace->recs.back().from_spill = from_spill;
-      trace->recs.back().size_before = init_size;
-    }
-    DevCtl ctl{};
-    ctl.size = init_size;
-    // adopt the freshest incumbent before starting
-    const int sb_now =
-        shared_best ? shared_best->load(std::memory_order_relaxed) : init_best;
-    ctl.best = sb_now < init_best ? sb_now : init_best;
-    if (trace) trace->recs[run_rec].best = ctl.best;
-    upload_ctl_pair(bufs.ctl.p, ctl, stream.s);
-    r.h2d += 2;
-    r.h2d_bytes += 2 * sizeof(DevCtl);
-    cfg.init_size = init_size;
-    const DevCtl fin = run_devpool_loop(stream.s, bufs.ctl.p, cfg, iter, r, shared_best,
-                                        hook, spill);
-    out.fin.tree += fin.tree;
-    out.fin.sol += fin.sol;
-    if (fin.best < out.fin.best) out.fin.best = fin.best;
-    r.gpu_iters += fin.iters;
-    if (trace) trace->recs[run_rec].size_after = fin.size;
-    if (fin.size > 0) {
-      const size_t base = leftover.size();
-      leftover.resize(base + fin.size);
-      HIP_CHECK(hipMemcpyAsync(leftover.data() + base, bufs.pool.p,
-                               fin.size * sizeof(NodeT), hipMemcpyDeviceToHost, stream.s));
-      HIP_CHECK(hipStreamSynchronize(stream.s));
-      r.d2h++;
-      r.d2h_bytes += fin.size * sizeof(NodeT);
-    }
-  };
-  // re-run anything the capacity spill pushed out (it may spill again; the
-  // stack shrinks by at least half the capacity per round)
-  auto drain_spilled = [&]() {
-    while (!spilled.empty()) {
-      const size_t take = std::min<size_t>(spilled.size(), capacity / 2);
-      std::vector<NodeT> chunk(spilled.end() - take, spilled.end());
-      spilled.resize(spilled.size() - take);
-      HIP_CHECK(hipMemcpyAsync(bufs.pool.p, chunk.data(), take * sizeof(NodeT),
-                               hipMemcpyHostToDevice, stream.s));
-      r.h2d++;
-      r.h2d_bytes += take * sizeof(NodeT);
-      run_pool(take, out.fin.best, /*from_spill=*/true);
-    }
-  };
-
-  int si;
-  while ((si = next_slice.fetch_add(1)) < static_cast<int>(slices.size())) {
-    const std::vector<NodeT>& nodes = slices[si];
-    if (nodes.empty()) continue;
-    if (nodes.size() > capacity) throw std::runtime_error("devpool capacity too small");
-    // per-stream async copies: synchronous hipMemcpy runs on the NULL stream
-    // and would serialize every slice thread at each slice boundary
-    HIP_CHECK(hipMemcpyAsync(bufs.pool.p, nodes.data(), nodes.size() * sizeof(NodeT),
-                             hipMemcpyHostToDevice, stream.s));
-    r.h2d++;
-    r.h2d_bytes += nodes.size() * sizeof(NodeT);
-    // a runner from here until the spilled stack is re-run too: with one
-    // scope per run_pool call a waiter that looked between two of them saw no
-    // runner and left for good while this thread still had nodes to share
-    RunnerScope runner(share);
-    run_pool(nodes.size(), best0);
-    drain_spilled();
-  }
-
-  // queue drained: take donated halves of still-running slices until no
-  // runner remains (ROADMAP item 2, landed)
-  while (share) {
-    StolenWork w;
-    if (!wait_for_work(*share, w)) break;
-    HIP_CHECK(hipMemcpyAsync(bufs.pool.p, w.src, w.n * sizeof(NodeT), hipMemcpyDeviceToDevice,
-                             stream.s));
-    HIP_CHECK(hipStreamSynchronize(stream.s));
-    ack_taken(*share);
-    if (trace) {  // what arrived, read from this thread's own pool
-      trace->recs.emplace_back();
-      DevLoopRec& rec = trace->recs.back();
-      rec.kind = DevLoopRec::TAKE;
-      rec.size_before = rec.size_after = w.n;
-      rec.best = w.best;
-      trace_nodes(*trace, rec, bufs.pool.p, w.n, /*on_device=*/true, stream.s);
-    }
-    RunnerScope runner(share);  // as above
-    run_pool(w.n, w.best);
-    drain_spilled();
-  }
-  return out;
 }
 
 static void merge_slice_diag(Result& r, const Result& d) {
@@ -1372,197 +850,6 @@ Result pfsp_gpu_from_pool(const std::vector<PFSPNode>& nodes, int inst,
 }
 
 // ---------------------------------------------------------------------------
-// Loop-driver test entry points (declared in engine_gpu.hpp): one slice
-// through the real devpool_thread, traced. Nothing else goes through them.
-// ---------------------------------------------------------------------------
-
-void validate_devpool_loop(size_t n, unsigned long long chunk, unsigned long long capacity,
-                           long long max_batches) {
-  if (capacity < 1 || capacity > LOOP_TRACE_MAX_NODES)
-    throw std::invalid_argument("capacity must be in 1..2^22 nodes");
-  if (chunk > capacity) throw std::invalid_argument("chunk must be <= capacity");
-  if (max_batches < 0 || max_batches > 4096)
-    throw std::invalid_argument("max_batches must be in 0..4096");
-  if (n == 0) throw std::invalid_argument("the pool must hold at least one node");
-}
-
-// Callers validate first: nothing here runs before their checks passed.
-template <class Problem>
-static DevpoolLoopOut<typename Problem::Node> devpool_loop_traced(
-    const Problem& problem, const std::vector<typename Problem::Node>& nodes, int best0,
-    unsigned long long m, unsigned long long chunk, unsigned long long capacity, bool graph,
-    int max_batches, std::atomic<int>* sb, long long lower_at, int lower_to, int device) {
-  using NodeT = typename Problem::Node;
-  DevpoolLoopOut<NodeT> out;
-  DevpoolThreadTest test;
-  test.chunk = chunk;
-  test.max_batches = max_batches;
-  test.trace = &out.trace;
-  const std::vector<std::vector<NodeT>> slices{nodes};
-  std::atomic<int> next_slice{0};
-  long long batch = 0;
-  const SliceReadbackFn<NodeT> lower = [&](const SliceReadback<NodeT>&) {
-    if (sb && batch++ == lower_at) {
-      int cur = sb->load(std::memory_order_relaxed);
-      while (lower_to < cur &&
-             !sb->compare_exchange_weak(cur, lower_to, std::memory_order_relaxed)) {
-      }
-    }
-  };
-  (void)hipGetLastError();  // drop a stale launch error of an earlier, unchecked call
-  const SliceOut so =
-      devpool_thread(problem, slices, next_slice, best0, static_cast<int>(m), /*M=*/0, device,
-                     capacity, sb, graph, /*share=*/nullptr, out.leftover, lower, &test);
-  out.tree = so.fin.tree;
-  out.sol = so.fin.sol;
-  out.iters = so.diag.gpu_iters;
-  out.best = so.fin.best;
-  if (sb) out.best = std::min(out.best, sb->load(std::memory_order_relaxed));
-  out.diag = so.diag;
-  out.trace.pool_d = nullptr;
-  return out;
-}
-
-DevpoolLoopOut<NQNode> nq_devpool_loop(const std::vector<NQNode>& nodes, int N, int g,
-                                       int finish, unsigned long long m,
-                                       unsigned long long chunk, unsigned long long capacity,
-                                       bool graph, int max_batches, int device) {
-  // before any HIP call
-  validate_nq_step(nodes, N, g, finish, m, chunk, capacity, "auto");
-  validate_devpool_loop(nodes.size(), chunk, capacity, max_batches);
-  if (m > (1ull << 30)) throw std::invalid_argument("m must be <= 2^30");
-  return devpool_loop_traced(NqDevProblem(N, g, finish), nodes, /*best0=*/0, m, chunk,
-                             capacity, graph, max_batches, nullptr, -1, 0, device);
-}
-
-DevpoolLoopOut<PFSPNode> pfsp_devpool_loop(const std::vector<PFSPNode>& nodes, int inst,
-                                           const std::string& lb, int best,
-                                           unsigned long long m, unsigned long long chunk,
-                                           unsigned long long capacity, bool graph,
-                                           int max_batches, const std::string& br,
-                                           long long lower_at, int lower_to, int device) {
-  // before any HIP call
-  validate_pfsp_step(nodes, inst, lb, m, chunk, capacity, /*geom=*/-1, "auto", br);
-  validate_devpool_loop(nodes.size(), chunk, capacity, max_batches);
-  if (m > (1ull << 30)) throw std::invalid_argument("m must be <= 2^30");
-  if (best < 1) throw std::invalid_argument("best must be >= 1");
-  if (lower_at < -1) throw std::invalid_argument("lower_best_at: batch must be >= 0");
-  if (lower_at >= 0 && lower_to < 1)
-    throw std::invalid_argument("lower_best_at: value must be >= 1");
-  const PfspInstance& I = pfsp_instance_cached(inst, 1, branching_from_string(br));
-  std::atomic<int> sb{best};
-  return devpool_loop_traced(
-      PfspDevProblem(I, devpool_lbk_geom(lbk_of(lb_from_string(lb)), I.machines)), nodes, best,
-      m, chunk, capacity, graph, max_batches, &sb, lower_at, lower_to, device);
-}
-
-// Share entry points: `threads` slice threads, one SliceShare, one slice.
-
-void validate_devpool_share(int threads, long long donate_floor, long long await_idle_ms) {
-  if (threads < 2 || threads > 4) throw std::invalid_argument("threads must be in 2..4");
-  if (donate_floor != 0 && donate_floor < 2)
-    throw std::invalid_argument("donate_floor must be 0 (the real floor) or >= 2");
-  if (await_idle_ms < 0 || await_idle_ms > 5000)
-    throw std::invalid_argument("await_idle_ms must be in 0..5000");
-}
-
-// Callers validate first: nothing here runs before their checks passed.
-template <class Problem>
-static std::vector<DevpoolLoopOut<typename Problem::Node>> devpool_share_traced(
-    const Problem& problem, const std::vector<typename Problem::Node>& nodes, int best0,
-    unsigned long long m, unsigned long long chunk, unsigned long long capacity,
-    int max_batches, std::atomic<int>* sb, int threads, unsigned long long donate_floor,
-    int await_idle_ms, int device) {
-  using NodeT = typename Problem::Node;
-  std::vector<DevpoolLoopOut<NodeT>> outs(threads);
-  std::vector<DevpoolThreadTest> tests(threads);
-  const std::vector<std::vector<NodeT>> slices{nodes};
-  std::atomic<int> next_slice{0};
-  SliceShare share;
-  std::vector<SliceOut> sos(threads);
-  std::vector<std::exception_ptr> errs(threads);
-  std::atomic<bool> first_done{false};
-  (void)hipGetLastError();  // drop a stale launch error of an earlier, unchecked call
-  std::vector<std::thread> pool;
-  for (int t = 0; t < threads; t++) {
-    tests[t].chunk = chunk;
-    tests[t].max_batches = max_batches;
-    tests[t].trace = &outs[t].trace;
-    tests[t].donate_floor = donate_floor;
-    tests[t].await_idle_ms = await_idle_ms;
-    tests[t].threads = threads;
-    pool.emplace_back([&, t] {
-      try {
-        sos[t] = devpool_thread(problem, slices, next_slice, best0, static_cast<int>(m),
-                                /*M=*/0, device, capacity, sb, /*allow_graph=*/false, &share,
-                                outs[t].leftover, {}, &tests[t]);
-      } catch (...) {
-        errs[t] = std::current_exception();
-      }
-      if (t == 0) first_done.store(true);
-    });
-    // a thread that reaches wait_for_work before the slice's owner counts as a
-    // runner leaves at once (the engines live with that); here the others
-    // start only once thread 0 runs the slice, or is through with it
-    if (t == 0) {
-      const auto deadline = std::chrono::steady_clock::now() + std::chrono::seconds(5);
-      while (!first_done.load() && std::chrono::steady_clock::now() < deadline) {
-        {
-          std::lock_guard<std::mutex> l(share.mu);
-          if (share.runners > 0) break;
-        }
-        std::this_thread::sleep_for(std::chrono::microseconds(200));
-      }
-    }
-  }
-  for (auto& th : pool) th.join();
-  for (auto& e : errs)
-    if (e) std::rethrow_exception(e);
-  for (int t = 0; t < threads; t++) {
-    DevpoolLoopOut<NodeT>& out = outs[t];
-    out.tree = sos[t].fin.tree;
-    out.sol = sos[t].fin.sol;
-    out.iters = sos[t].diag.gpu_iters;
-    out.best = sos[t].fin.best;
-    out.diag = sos[t].diag;
-    out.trace.pool_d = nullptr;
-  }
-  return outs;
-}
-
-std::vector<DevpoolLoopOut<NQNode>> nq_devpool_share(
-    const std::vector<NQNode>& nodes, int N, int g, int finish, unsigned long long m,
-    unsigned long long chunk, unsigned long long capacity, int max_batches, int threads,
-    unsigned long long donate_floor, int await_idle_ms, int device) {
-  // before any HIP call
-  validate_nq_step(nodes, N, g, finish, m, chunk, capacity, "auto");
-  validate_devpool_loop(nodes.size(), chunk, capacity, max_batches);
-  validate_devpool_share(threads, static_cast<long long>(donate_floor), await_idle_ms);
-  if (m > (1ull << 30)) throw std::invalid_argument("m must be <= 2^30");
-  return devpool_share_traced(NqDevProblem(N, g, finish), nodes, /*best0=*/0, m, chunk,
-                              capacity, max_batches, nullptr, threads, donate_floor,
-                              await_idle_ms, device);
-}
-
-std::vector<DevpoolLoopOut<PFSPNode>> pfsp_devpool_share(
-    const std::vector<PFSPNode>& nodes, int inst, const std::string& lb, int best,
-    unsigned long long m, unsigned long long chunk, unsigned long long capacity,
-    int max_batches, const std::string& br, int threads, unsigned long long donate_floor,
-    int await_idle_ms, int device) {
-  // before any HIP call
-  validate_pfsp_step(nodes, inst, lb, m, chunk, capacity, /*geom=*/-1, "auto", br);
-  validate_devpool_loop(nodes.size(), chunk, capacity, max_batches);
-  validate_devpool_share(threads, static_cast<long long>(donate_floor), await_idle_ms);
-  if (m > (1ull << 30)) throw std::invalid_argument("m must be <= 2^30");
-  if (best < 1) throw std::invalid_argument("best must be >= 1");
-  const PfspInstance& I = pfsp_instance_cached(inst, 1, branching_from_string(br));
-  std::atomic<int> sb{best};
-  return devpool_share_traced(
-      PfspDevProblem(I, devpool_lbk_geom(lbk_of(lb_from_string(lb)), I.machines)), nodes, best,
-      m, chunk, capacity, max_batches, &sb, threads, donate_floor, await_idle_ms, device);
-}
-
-// ---------------------------------------------------------------------------
 // Device-built frontiers (declared in engine_gpu.hpp)
 // ---------------------------------------------------------------------------
 
@@ -1751,12 +1038,7 @@ PfspAsyncEngine::~PfspAsyncEngine() {
 
 int PfspAsyncEngine::best() const { return shared_best_.load(std::memory_order_relaxed); }
 
-void PfspAsyncEngine::update_best(int b) {
-  int cur = shared_best_.load(std::memory_order_relaxed);
-  while (b < cur &&
-         !shared_best_.compare_exchange_weak(cur, b, std::memory_order_relaxed)) {
-  }
-}
+void PfspAsyncEngine::update_best(int b) { min_into(shared_best_, b); }
 
 bool PfspAsyncEngine::done() const {
   std::lock_guard<std::mutex> l(mu_);

@@ -1,6 +1,5 @@
 // Public API of the single-GPU engines (implemented in engine_gpu.cpp; the
-// test-only entry points at the end in engine_testing.cpp, except the
-// loop-driver ones, which sit next to the slice thread they run).
+// test-only entry points at the end in engine_testing.cpp).
 #pragma once
 #include <atomic>
 #include <condition_variable>
@@ -250,8 +249,8 @@ std::vector<DevpoolSnapshot<PFSPNode>> pfsp_devpool_chain(
     unsigned long long capacity, int geom, const std::string& presum, int device,
     const std::string& br = "fwd");
 
-// Loop-driver entry points (driver-level tests; implemented in engine_gpu.cpp
-// next to the code they run): ONE slice goes through the real slice thread —
+// Loop-driver entry points (driver-level tests): ONE slice goes through the
+// real slice thread and loop driver (devpool_driver.hpp) —
 // run_pool, the loop driver, the capacity spill, drain_spilled and the
 // leftover copy — with no SliceShare, the chunk cap `chunk` taken as given
 // (no --M floor, no environment variable) and graph replay allowed or not by
@@ -306,8 +305,6 @@ struct DevLoopRec {
 struct DevLoopTrace {
   std::vector<DevLoopRec> recs;
   unsigned long long traced_nodes = 0;
-  const void* pool_d = nullptr;  // set by the slice thread
-  size_t node_bytes = 0;
 };
 template <class NodeT>
 struct DevpoolLoopOut {

@@ -1,6 +1,6 @@
 // Internals shared by the engine translation units (engine_gpu.cpp,
 // engine_multi.cpp, engine_testing.cpp): HIP error check, cached device /
-// pinned memory and streams, the PFSP table caches, and the pieces every
+// pinned memory and streams, the PFSP table caches, min_into, and the pieces every
 // devpool caller is built from — the owning buffer set, the per-problem
 // descriptors and the per-iteration launch policy. Not part of the public
 // API: bindings.cpp sees engine_gpu.hpp only.
@@ -8,6 +8,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <atomic>
 #include <memory>
 #include <stdexcept>
 #include <string>
@@ -25,6 +26,13 @@ namespace gats {
       throw std::runtime_error(std::string("HIP error: ") + hipGetErrorString(_e) +  \
                                " at " #expr);                                        \
   } while (0)
+
+// Lower the shared incumbent `a` to `v` unless it is already that low.
+inline void min_into(std::atomic<int>& a, int v) {
+  int cur = a.load(std::memory_order_relaxed);
+  while (v < cur && !a.compare_exchange_weak(cur, v, std::memory_order_relaxed)) {
+  }
+}
 
 // Process-level buffer cache (engine_gpu.cpp): buffers are recycled by exact
 // (device, bytes) and freed only at process exit.

@@ -1,15 +1,22 @@
 // Test-only entry points of the GPU engines (declared in engine_gpu.hpp): host
 // validation, single devpool iterations and iteration chains built from the
 // engines' own buffer set, problem descriptors and launch policy
-// (engine_internal.hpp), and the eval-only kernels. No search runs through
+// (engine_internal.hpp), traced runs of the real slice thread and loop driver
+// (devpool_driver.hpp), and the eval-only kernels. No engine runs through
 // this file.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <atomic>
+#include <chrono>
+#include <cstring>
+#include <mutex>
 #include <stdexcept>
 #include <string>
+#include <thread>
 #include <vector>
 
+#include "devpool_driver.hpp"
 #include "engine_gpu.hpp"
 #include "engine_internal.hpp"
 #include "gpu_api.hpp"
@@ -44,6 +51,10 @@ void validate_step_window(size_t n, int per, unsigned long long m, unsigned long
   if (capacity < n) throw std::invalid_argument("capacity must be >= the number of nodes");
 }
 
+DevpoolStepCtl step_ctl_of(const DevCtl& c) {
+  return {c.size, c.chunk, c.tree, c.sol, c.iters, c.best, c.overflow};
+}
+
 template <class NodeT>
 DevpoolStepCtl step_readback(std::vector<NodeT>& nodes, const NodeT* pool_d,
                              const DevCtl* ctl_next_d, unsigned long long capacity,
@@ -58,7 +69,7 @@ DevpoolStepCtl step_readback(std::vector<NodeT>& nodes, const NodeT* pool_d,
                              hipMemcpyDeviceToHost, s));
     HIP_CHECK(hipStreamSynchronize(s));
   }
-  return {fin.size, fin.chunk, fin.tree, fin.sol, fin.iters, fin.best, fin.overflow};
+  return step_ctl_of(fin);
 }
 
 }  // namespace
@@ -286,7 +297,7 @@ std::vector<DevpoolSnapshot<typename Problem::Node>> devpool_chain(
     if (keep > 0)
       HIP_CHECK(hipMemcpyAsync(out[i].nodes.data(), snap_pool_d.p + i * capacity,
                                keep * sizeof(NodeT), hipMemcpyDeviceToHost, s));
-    out[i].ctl = {f.size, f.chunk, f.tree, f.sol, f.iters, f.best, f.overflow};
+    out[i].ctl = step_ctl_of(f);
   }
   HIP_CHECK(hipStreamSynchronize(s));
   return out;
@@ -315,6 +326,278 @@ std::vector<DevpoolSnapshot<PFSPNode>> pfsp_devpool_chain(
   const PfspInstance& I = pfsp_instance_cached(inst, 1, branching_from_string(br));
   return devpool_chain(pfsp_step_problem(I, lb, geom), nodes, best, m, windows, capacity,
                        presum_mode(presum), device);
+}
+
+// ---------------------------------------------------------------------------
+// Loop-driver test entry points (declared in engine_gpu.hpp): one slice
+// through the real devpool_thread (devpool_driver.hpp), traced. Nothing else
+// goes through them.
+// ---------------------------------------------------------------------------
+
+namespace {
+
+constexpr unsigned long long LOOP_TRACE_MAX_NODES = 1ull << 22;
+
+// The observer of the traced runs: one DevLoopRec per call, nodes copied over
+// the thread's idle stream. The copies are not counted in the diag counters.
+class LoopRecorder : public DevLoopObserver {
+ public:
+  LoopRecorder(DevLoopTrace& t, size_t node_bytes, unsigned long long capacity)
+      : t_(t), node_bytes_(node_bytes), capacity_(capacity) {}
+
+  void run_begin(bool from_spill, unsigned long long size, int best) override {
+    run_ = t_.recs.size();
+    DevLoopRec& rec = add(DevLoopRec::RUN, size);
+    rec.from_spill = from_spill;
+    rec.best = best;
+  }
+  void run_end(unsigned long long leftover) override { t_.recs[run_].size_after = leftover; }
+  void batch(int b, int parity, bool replayed, bool captured, unsigned long long size_before,
+             const DevCtl& ctl, const void* pool_d, hipStream_t s) override {
+    DevLoopRec& rec = add(DevLoopRec::BATCH, size_before);
+    rec.b = b;
+    rec.parity = parity;
+    rec.graph = replayed;
+    rec.captured = captured;
+    rec.ctl = step_ctl_of(ctl);
+    if (ctl.overflow) return;
+    if (ctl.size > capacity_) throw std::runtime_error("devpool loop: size exceeds capacity");
+    trace_nodes(rec, pool_d, ctl.size, &s);
+  }
+  void spill(unsigned long long size_before, unsigned long long size_after, const void* moved,
+             unsigned long long n) override {
+    DevLoopRec& rec = add(DevLoopRec::SPILL, size_before);
+    rec.size_after = size_after;
+    trace_nodes(rec, moved, n, nullptr);
+  }
+  void donate_carve(unsigned long long size_before, unsigned long long kept, int best,
+                    const void* offered_d, hipStream_t s) override {
+    DevLoopRec& rec = add(DevLoopRec::DONATE, size_before);
+    rec.best = best;
+    trace_nodes(rec, offered_d, size_before - kept, &s);
+  }
+  void donate_end(Donation outcome, unsigned long long size_after) override {
+    if (outcome == Donation::NONE) return;  // no carve, no record
+    t_.recs.back().size_after = size_after;
+    t_.recs.back().outcome = static_cast<int>(outcome);
+  }
+  void take(unsigned long long n, int best, const void* pool_d, hipStream_t s) override {
+    DevLoopRec& rec = add(DevLoopRec::TAKE, n);
+    rec.size_after = n;
+    rec.best = best;
+    trace_nodes(rec, pool_d, n, &s);
+  }
+
+ private:
+  DevLoopRec& add(int kind, unsigned long long size_before) {
+    t_.recs.emplace_back();
+    t_.recs.back().kind = kind;
+    t_.recs.back().size_before = size_before;
+    return t_.recs.back();
+  }
+  // Copy `n` nodes into a record: from device memory over the (idle) stream
+  // `*s`, or from host memory when `s` is null.
+  void trace_nodes(DevLoopRec& rec, const void* src, unsigned long long n,
+                   const hipStream_t* s) {
+    t_.traced_nodes += n;
+    if (t_.traced_nodes > LOOP_TRACE_MAX_NODES)
+      throw std::runtime_error("devpool loop trace exceeds 2^22 nodes");
+    rec.nodes.resize(n * node_bytes_);
+    if (n == 0) return;
+    if (!s) {
+      std::memcpy(rec.nodes.data(), src, rec.nodes.size());
+      return;
+    }
+    HIP_CHECK(hipMemcpyAsync(rec.nodes.data(), src, rec.nodes.size(), hipMemcpyDeviceToHost, *s));
+    HIP_CHECK(hipStreamSynchronize(*s));
+  }
+
+  DevLoopTrace& t_;
+  const size_t node_bytes_;
+  const unsigned long long capacity_;
+  size_t run_ = 0;  // the open RUN record
+};
+
+}  // namespace
+
+void validate_devpool_loop(size_t n, unsigned long long chunk, unsigned long long capacity,
+                           long long max_batches) {
+  if (capacity < 1 || capacity > LOOP_TRACE_MAX_NODES)
+    throw std::invalid_argument("capacity must be in 1..2^22 nodes");
+  if (chunk > capacity) throw std::invalid_argument("chunk must be <= capacity");
+  if (max_batches < 0 || max_batches > 4096)
+    throw std::invalid_argument("max_batches must be in 0..4096");
+  if (n == 0) throw std::invalid_argument("the pool must hold at least one node");
+}
+
+// Callers validate first: nothing here runs before their checks passed.
+template <class Problem>
+DevpoolLoopOut<typename Problem::Node> devpool_loop_traced(
+    const Problem& problem, const std::vector<typename Problem::Node>& nodes, int best0,
+    unsigned long long m, unsigned long long chunk, unsigned long long capacity, bool graph,
+    int max_batches, std::atomic<int>* sb, long long lower_at, int lower_to, int device) {
+  using NodeT = typename Problem::Node;
+  DevpoolLoopOut<NodeT> out;
+  DevpoolThreadTest test;
+  test.chunk = chunk;
+  test.max_batches = max_batches;
+  LoopRecorder rec(out.trace, sizeof(NodeT), capacity);
+  const std::vector<std::vector<NodeT>> slices{nodes};
+  std::atomic<int> next_slice{0};
+  long long batch = 0;
+  const SliceReadbackFn<NodeT> lower = [&](const SliceReadback<NodeT>&) {
+    if (sb && batch++ == lower_at) min_into(*sb, lower_to);
+  };
+  (void)hipGetLastError();  // drop a stale launch error of an earlier, unchecked call
+  const SliceOut so =
+      devpool_thread(problem, slices, next_slice, best0, static_cast<int>(m), /*M=*/0, device,
+                     capacity, sb, graph, /*share=*/nullptr, out.leftover, lower, &test, &rec);
+  out.tree = so.fin.tree;
+  out.sol = so.fin.sol;
+  out.iters = so.diag.gpu_iters;
+  out.best = so.fin.best;
+  if (sb) out.best = std::min(out.best, sb->load(std::memory_order_relaxed));
+  out.diag = so.diag;
+  return out;
+}
+
+DevpoolLoopOut<NQNode> nq_devpool_loop(const std::vector<NQNode>& nodes, int N, int g,
+                                       int finish, unsigned long long m,
+                                       unsigned long long chunk, unsigned long long capacity,
+                                       bool graph, int max_batches, int device) {
+  // before any HIP call
+  validate_nq_step(nodes, N, g, finish, m, chunk, capacity, "auto");
+  validate_devpool_loop(nodes.size(), chunk, capacity, max_batches);
+  if (m > (1ull << 30)) throw std::invalid_argument("m must be <= 2^30");
+  return devpool_loop_traced(NqDevProblem(N, g, finish), nodes, /*best0=*/0, m, chunk,
+                             capacity, graph, max_batches, nullptr, -1, 0, device);
+}
+
+DevpoolLoopOut<PFSPNode> pfsp_devpool_loop(const std::vector<PFSPNode>& nodes, int inst,
+                                           const std::string& lb, int best,
+                                           unsigned long long m, unsigned long long chunk,
+                                           unsigned long long capacity, bool graph,
+                                           int max_batches, const std::string& br,
+                                           long long lower_at, int lower_to, int device) {
+  // before any HIP call
+  validate_pfsp_step(nodes, inst, lb, m, chunk, capacity, /*geom=*/-1, "auto", br);
+  validate_devpool_loop(nodes.size(), chunk, capacity, max_batches);
+  if (m > (1ull << 30)) throw std::invalid_argument("m must be <= 2^30");
+  if (best < 1) throw std::invalid_argument("best must be >= 1");
+  if (lower_at < -1) throw std::invalid_argument("lower_best_at: batch must be >= 0");
+  if (lower_at >= 0 && lower_to < 1)
+    throw std::invalid_argument("lower_best_at: value must be >= 1");
+  const PfspInstance& I = pfsp_instance_cached(inst, 1, branching_from_string(br));
+  std::atomic<int> sb{best};
+  return devpool_loop_traced(
+      PfspDevProblem(I, devpool_lbk_geom(lbk_of(lb_from_string(lb)), I.machines)), nodes, best,
+      m, chunk, capacity, graph, max_batches, &sb, lower_at, lower_to, device);
+}
+
+// Share entry points: `threads` slice threads, one SliceShare, one slice.
+
+void validate_devpool_share(int threads, long long donate_floor, long long await_idle_ms) {
+  if (threads < 2 || threads > 4) throw std::invalid_argument("threads must be in 2..4");
+  if (donate_floor != 0 && donate_floor < 2)
+    throw std::invalid_argument("donate_floor must be 0 (the real floor) or >= 2");
+  if (await_idle_ms < 0 || await_idle_ms > 5000)
+    throw std::invalid_argument("await_idle_ms must be in 0..5000");
+}
+
+// Callers validate first: nothing here runs before their checks passed.
+template <class Problem>
+std::vector<DevpoolLoopOut<typename Problem::Node>> devpool_share_traced(
+    const Problem& problem, const std::vector<typename Problem::Node>& nodes, int best0,
+    unsigned long long m, unsigned long long chunk, unsigned long long capacity,
+    int max_batches, std::atomic<int>* sb, int threads, unsigned long long donate_floor,
+    int await_idle_ms, int device) {
+  using NodeT = typename Problem::Node;
+  std::vector<DevpoolLoopOut<NodeT>> outs(threads);
+  std::vector<DevpoolThreadTest> tests(threads);
+  std::vector<LoopRecorder> recs;
+  for (auto& o : outs) recs.emplace_back(o.trace, sizeof(NodeT), capacity);
+  const std::vector<std::vector<NodeT>> slices{nodes};
+  std::atomic<int> next_slice{0};
+  SliceShare share;
+  std::vector<SliceOut> sos(threads);
+  std::vector<std::exception_ptr> errs(threads);
+  std::atomic<bool> first_done{false};
+  (void)hipGetLastError();  // drop a stale launch error of an earlier, unchecked call
+  std::vector<std::thread> pool;
+  for (int t = 0; t < threads; t++) {
+    tests[t].chunk = chunk;
+    tests[t].max_batches = max_batches;
+    tests[t].donate_floor = donate_floor;
+    tests[t].await_idle_ms = await_idle_ms;
+    tests[t].threads = threads;
+    pool.emplace_back([&, t] {
+      try {
+        sos[t] = devpool_thread(problem, slices, next_slice, best0, static_cast<int>(m),
+                                /*M=*/0, device, capacity, sb, /*allow_graph=*/false, &share,
+                                outs[t].leftover, {}, &tests[t], &recs[t]);
+      } catch (...) {
+        errs[t] = std::current_exception();
+      }
+      if (t == 0) first_done.store(true);
+    });
+    // a thread that reaches wait_for_work before the slice's owner counts as a
+    // runner leaves at once (the engines live with that); here the others
+    // start only once thread 0 runs the slice, or is through with it
+    if (t == 0) {
+      const auto deadline = std::chrono::steady_clock::now() + std::chrono::seconds(5);
+      while (!first_done.load() && std::chrono::steady_clock::now() < deadline) {
+        {
+          std::lock_guard<std::mutex> l(share.mu);
+          if (share.runners > 0) break;
+        }
+        std::this_thread::sleep_for(std::chrono::microseconds(200));
+      }
+    }
+  }
+  for (auto& th : pool) th.join();
+  for (auto& e : errs)
+    if (e) std::rethrow_exception(e);
+  for (int t = 0; t < threads; t++) {
+    DevpoolLoopOut<NodeT>& out = outs[t];
+    out.tree = sos[t].fin.tree;
+    out.sol = sos[t].fin.sol;
+    out.iters = sos[t].diag.gpu_iters;
+    out.best = sos[t].fin.best;
+    out.diag = sos[t].diag;
+  }
+  return outs;
+}
+
+std::vector<DevpoolLoopOut<NQNode>> nq_devpool_share(
+    const std::vector<NQNode>& nodes, int N, int g, int finish, unsigned long long m,
+    unsigned long long chunk, unsigned long long capacity, int max_batches, int threads,
+    unsigned long long donate_floor, int await_idle_ms, int device) {
+  // before any HIP call
+  validate_nq_step(nodes, N, g, finish, m, chunk, capacity, "auto");
+  validate_devpool_loop(nodes.size(), chunk, capacity, max_batches);
+  validate_devpool_share(threads, static_cast<long long>(donate_floor), await_idle_ms);
+  if (m > (1ull << 30)) throw std::invalid_argument("m must be <= 2^30");
+  return devpool_share_traced(NqDevProblem(N, g, finish), nodes, /*best0=*/0, m, chunk,
+                              capacity, max_batches, nullptr, threads, donate_floor,
+                              await_idle_ms, device);
+}
+
+std::vector<DevpoolLoopOut<PFSPNode>> pfsp_devpool_share(
+    const std::vector<PFSPNode>& nodes, int inst, const std::string& lb, int best,
+    unsigned long long m, unsigned long long chunk, unsigned long long capacity,
+    int max_batches, const std::string& br, int threads, unsigned long long donate_floor,
+    int await_idle_ms, int device) {
+  // before any HIP call
+  validate_pfsp_step(nodes, inst, lb, m, chunk, capacity, /*geom=*/-1, "auto", br);
+  validate_devpool_loop(nodes.size(), chunk, capacity, max_batches);
+  validate_devpool_share(threads, static_cast<long long>(donate_floor), await_idle_ms);
+  if (m > (1ull << 30)) throw std::invalid_argument("m must be <= 2^30");
+  if (best < 1) throw std::invalid_argument("best must be >= 1");
+  const PfspInstance& I = pfsp_instance_cached(inst, 1, branching_from_string(br));
+  std::atomic<int> sb{best};
+  return devpool_share_traced(
+      PfspDevProblem(I, devpool_lbk_geom(lbk_of(lb_from_string(lb)), I.machines)), nodes, best,
+      m, chunk, capacity, max_batches, &sb, threads, donate_floor, await_idle_ms, device);
 }
 
 // ---------------------------------------------------------------------------
