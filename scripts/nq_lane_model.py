@@ -147,6 +147,51 @@ def schedule(jobs, N, S, dynamic, qcap=None):
     return work, cost + run(cur), entries
 
 
+def run_waves(lengths, T, nwaves=LANES // WAVE):
+    """The batched refill (nq_refill_now) on one round's entries: nwaves waves
+    of WAVE lockstep lanes on one queue head; a wave fetches for all of its
+    idle lanes when it is not drained and T of them, or all, are idle. The
+    wave that is furthest behind in time moves next. Returns (iterations,
+    iterations that executed the fetch path), summed over the waves."""
+    left = [[0] * WAVE for _ in range(nwaves)]  # iterations left per lane
+    drained = [False] * nwaves
+    clock = [(0, w) for w in range(nwaves)]
+    head = iters = fetches = 0
+    while clock:
+        t, w = heapq.heappop(clock)
+        lanes = left[w]
+        idle = [i for i, r in enumerate(lanes) if r == 0]
+        if not drained[w] and idle and (len(idle) >= T or len(idle) == WAVE):
+            got, head = head, head + len(idle)
+            drained[w] = got + len(idle) >= len(lengths)
+            for k, i in enumerate(idle):
+                if got + k < len(lengths):
+                    lanes[i] = lengths[got + k]
+            fetches += 1
+        elif drained[w] and len(idle) == WAVE:
+            continue  # the wave leaves
+        left[w] = [r - 1 if r else 0 for r in lanes]
+        iters += 1
+        heapq.heappush(clock, (t + 1, w))
+    return iters, fetches
+
+
+def schedule_waves(jobs, N, S, T, qcap):
+    """(work, iterations, fetch iterations) of one tile, in rounds of qcap."""
+    groups = [[flat_iters(*sj, N) for sj in split(j, N, S)] for j in jobs]
+    work = sum(map(sum, groups))
+    iters = fetches = 0
+    cur = []
+    for g in groups + [None]:
+        if g is None or (cur and len(cur) + len(g) > qcap):
+            i, f = run_waves(cur, T)
+            iters, fetches = iters + i, fetches + f
+            cur = []
+        if g:
+            cur += g
+    return work, iters, fetches
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--tiles", type=int, default=24)
@@ -176,6 +221,21 @@ def main():
             work, cost, entries = work + w, cost + c, entries + e
         base = base or cost
         print(f"{name:34s} {entries / a.tiles:8.0f} {work / cost:9.2f} {cost / base:13.2f}")
+    # Wave-level accounting of the batched refill (split 2, queue 1728): a
+    # wave iteration costs 1, one that executes the fetch path costs F; summed
+    # over the block's waves, per tile, in thousands of step costs.
+    fs = (1.0, 1.5, 2.0)
+    print()
+    print("split 2, queue 1728, four waves on one queue head; refill when >= T lanes are idle")
+    print(f"{'T':>4s} {'fetch iters':>11s} {'lane eff.':>9s} " +
+          " ".join(f"{'cost F=' + str(f):>11s}" for f in fs) + "   (per tile)")
+    for T in (1, 4, 8, 12, 16, 24, 32, 64):
+        work = iters = fetches = 0
+        for jobs in tiles:
+            w, i, f = schedule_waves(jobs, a.N, 2, T, 1728)
+            work, iters, fetches = work + w, iters + i, fetches + f
+        print(f"{T:4d} {fetches / a.tiles:11.0f} {work / (iters * WAVE):9.2f} " +
+              " ".join(f"{(iters + (f - 1) * fetches) / a.tiles:11.0f}" for f in fs))
 
 
 if __name__ == "__main__":

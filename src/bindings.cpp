@@ -169,6 +169,146 @@ py::tuple nq_finish_block_cpu(const std::vector<std::array<uint32_t, 4>>& jobs, 
                 : nq_finish_block<false>(jobs, N, g, split, static_cast<uint32_t>(qcap));
 }
 
+// CPU run of k_nq_x's drain as its waves run it: `waves` x `lanes` flat walks
+// stepped in lockstep, every wave deciding with the kernel's own rule
+// (nq_refill_now / nq_refill_drains / nq_wave_done) when its idle lanes fetch,
+// the waves taking turns, one loop iteration each, on one queue head. The
+// split pass, the rounds and the entries are nq_finish_block's. Returns
+// (tree, sol, entries, rounds, refills, steps); steps counts the waves' loop
+// iterations. Every iteration but a wave's last either steps an active lane
+// or is a refill, and the lane steps of a round sum to the walk lengths of
+// its sub-jobs whichever lane walks them, so steps <= walk lengths + refills:
+// the loop throws when it passes that bound instead of spinning.
+template <bool G1>
+py::tuple nq_finish_wave(const std::vector<std::array<uint32_t, 4>>& jobs, int N, int g, int split,
+                         uint32_t qcap, uint32_t T, uint32_t lanes, uint32_t waves) {
+  using Flat = NqFlat<NQ_FLAT_LEVELS_DEV>;
+  const uint32_t msk = (1u << N) - 1u;
+  const uint32_t njobs = static_cast<uint32_t>(jobs.size());
+  auto levels = [&](uint32_t q) {
+    return nq_split_levels(split, N - static_cast<int>(jobs[q][3]));
+  };
+  std::vector<uint32_t> off(njobs + 1, 0);
+  uint32_t nodes = 0;
+  for (uint32_t q = 0; q < njobs; q++) {
+    const uint32_t n = nq_split_job<G1, false>(jobs[q][0], jobs[q][1], jobs[q][2], levels(q), msk,
+                                               g, nodes, [](uint32_t, uint32_t, uint32_t) {});
+    if (n > qcap)
+      throw std::invalid_argument("qcap " + std::to_string(qcap) + " is below the " +
+                                  std::to_string(n) + " sub-jobs of job " + std::to_string(q));
+    off[q + 1] = off[q] + n;
+  }
+  auto load = [&](Flat& w, uint32_t e) {
+    const auto& j = jobs[nq_sub_ref(e)];
+    nq_sub_load<G1>(w, e, j[0], j[1], j[2], static_cast<int>(j[3]), N, msk, g);
+  };
+  auto step = [&](Flat& w) {  // the kernel's loop body below the fetch
+    if (w.cand == 0 && w.stack > 1) w.pop(msk);
+    if (w.cand) w.template take<G1>(msk, g);
+  };
+  std::vector<Flat> st(static_cast<size_t>(waves) * lanes);
+  for (auto& w : st) w.tree = w.sol = 0;
+  std::vector<uint32_t> subq(qcap);
+  uint64_t refills = 0, steps = 0;
+  uint32_t rounds = 0;
+  for (uint32_t jb = 0; jb < njobs; rounds++) {
+    const uint32_t je = nq_round_end(off.data(), jb, njobs, qcap);
+    const uint32_t nsub = off[je] - off[jb];
+    for (uint32_t q = jb; q < je; q++) {
+      uint32_t w = off[q] - off[jb], unused = 0;
+      nq_split_job<true, true>(jobs[q][0], jobs[q][1], jobs[q][2], levels(q), msk, 1, unused,
+                               [&](uint32_t nc, uint32_t c1, uint32_t c2) {
+                                 subq[w++] = nq_sub_encode(q, nc, c1, c2);
+                               });
+    }
+    uint64_t walk = 0;  // the round's bound: one lane walks every entry
+    for (uint32_t i = 0; i < nsub; i++) {
+      Flat w;
+      w.tree = w.sol = 0;
+      for (load(w, subq[i]); !nq_lane_idle(w.cand, w.stack); walk++) step(w);
+    }
+    const uint64_t steps0 = steps, refills0 = refills;
+    uint32_t head = 0, running = waves;
+    std::vector<char> drained(waves, 0), done(waves, 0);
+    for (auto& w : st) w.cand = 0, w.stack = 0;
+    while (running) {
+      for (uint32_t v = 0; v < waves; v++) {
+        if (done[v]) continue;
+        Flat* wl = &st[static_cast<size_t>(v) * lanes];
+        uint32_t nidle = 0;
+        for (uint32_t l = 0; l < lanes; l++) nidle += nq_lane_idle(wl[l].cand, wl[l].stack);
+        if (nq_refill_now(nidle, lanes, T, drained[v] != 0)) {
+          const uint32_t got = head;
+          head += nidle;
+          refills++;
+          drained[v] = nq_refill_drains(got, nidle, nsub);
+          uint32_t qi = got;
+          for (uint32_t l = 0; l < lanes; l++)
+            if (nq_lane_idle(wl[l].cand, wl[l].stack)) {
+              if (qi < nsub) load(wl[l], subq[qi]);
+              qi++;
+            }
+        } else if (nq_wave_done(nidle, lanes, drained[v] != 0)) {
+          done[v] = 1;
+          running--;
+          continue;
+        }
+        for (uint32_t l = 0; l < lanes; l++) step(wl[l]);
+        steps++;
+        if (steps - steps0 > walk + (refills - refills0))
+          throw std::runtime_error("the drain passed its bound of " + std::to_string(walk) +
+                                   " lane steps + " + std::to_string(refills - refills0) +
+                                   " refills in round " + std::to_string(rounds));
+      }
+    }
+    jb = je;
+  }
+  uint64_t tree = nodes, sol = 0;
+  for (const auto& w : st) tree += w.tree, sol += w.sol;
+  return py::make_tuple(tree, sol, off[njobs], rounds, refills, steps);
+}
+
+py::tuple nq_finish_wave_cpu(const std::vector<std::array<uint32_t, 4>>& jobs, int N, int g,
+                             int split, long long qcap, int refill, int lanes, int waves) {
+  if (N < 1 || N > MAX_JOBS) throw std::invalid_argument("N must be in 1..20");
+  if (g < 1) throw std::invalid_argument("g must be >= 1");
+  if (split < 1 || split > NQ_SPLIT_MAX) throw std::invalid_argument("split must be in 1..2");
+  if (qcap < 1 || qcap > (1 << 20)) throw std::invalid_argument("qcap must be in 1..2^20");
+  if (lanes < 1 || lanes > 64) throw std::invalid_argument("lanes must be in 1..64");
+  if (waves < 1 || waves > 16) throw std::invalid_argument("waves must be in 1..16");
+  // a threshold above the wave's width is rejected, not clamped: it could only
+  // ever act as the all-idle rule, which `refill == lanes` already names
+  if (refill < 1 || refill > lanes) throw std::invalid_argument("refill must be in 1..lanes");
+  if (jobs.size() > 1024) throw std::invalid_argument("a block holds at most 1024 jobs");
+  for (const auto& j : jobs) {
+    const int rows = N - static_cast<int>(j[3]);
+    if (rows < 1 || rows > NQ_FLAT_LEVELS_DEV)
+      throw std::invalid_argument("every job needs 1..8 empty rows");
+    if ((j[0] | j[1] | j[2]) >> N) throw std::invalid_argument("mask bits at or above column N");
+  }
+  const auto q = static_cast<uint32_t>(qcap);
+  const auto T = static_cast<uint32_t>(refill);
+  const auto L = static_cast<uint32_t>(lanes), W = static_cast<uint32_t>(waves);
+  return g == 1 ? nq_finish_wave<true>(jobs, N, g, split, q, T, L, W)
+                : nq_finish_wave<false>(jobs, N, g, split, q, T, L, W);
+}
+
+// The packed parent masks and the job reference, for tests.
+py::tuple nq_pmask_unpack_py(uint64_t w) {
+  uint32_t c, d1, d2;
+  nq_pmask_unpack(w, c, d1, d2);
+  return py::make_tuple(c, d1, d2);
+}
+
+// (cols, d1, d2, row): the job below child column `ref & 31` of the parent
+// whose packed masks are `w`, as nq_finish_count_cpu takes it.
+py::tuple nq_job_state_py(uint64_t w, uint32_t ref, int N) {
+  if (N < 1 || N > MAX_JOBS) throw std::invalid_argument("N must be in 1..20");
+  uint32_t c, d1, d2;
+  const int row = nq_job_state(w, ref, (1u << N) - 1u, c, d1, d2);
+  return py::make_tuple(c, d1, d2, row);
+}
+
 // The sub-job queue entry codec, for tests: encode, and decode to
 // (ref, ncols, c1, c2).
 py::tuple nq_sub_decode_py(uint32_t e) {
@@ -410,7 +550,7 @@ py::dict step_ctl_to_dict(const DevpoolStepCtl& c) {
 
 py::tuple nq_devpool_step_py(const py::bytes& nodes, int N, int g, int finish, long long m,
                              const py::object& M, const py::object& capacity,
-                             const std::string& presum, int device, int split) {
+                             const std::string& presum, int device, int split, int refill) {
   auto v = nodes_from_bytes<NQNode>(nodes);
   if (m < 0) throw std::invalid_argument("m must be >= 1");
   const unsigned long long Mv = step_arg(M, v.empty() ? 1 : v.size(), "M");
@@ -419,7 +559,7 @@ py::tuple nq_devpool_step_py(const py::bytes& nodes, int N, int g, int finish, l
   {
     py::gil_scoped_release rel;
     c = nq_devpool_step(v, N, g, finish, static_cast<unsigned long long>(m), Mv, cap, presum,
-                        device, split);
+                        device, split, refill);
   }
   return py::make_tuple(nodes_to_bytes(v.data(), v.size()), step_ctl_to_dict(c));
 }
@@ -464,7 +604,7 @@ py::list chain_to_list(const std::vector<DevpoolSnapshot<NodeT>>& snaps) {
 
 py::list nq_devpool_chain_py(const py::bytes& nodes, int N, const std::vector<long long>& windows,
                              int g, int finish, long long m, const py::object& capacity,
-                             const std::string& presum, int device, int split) {
+                             const std::string& presum, int device, int split, int refill) {
   auto v = nodes_from_bytes<NQNode>(nodes);
   if (m < 0) throw std::invalid_argument("m must be >= 1");
   const auto w = chain_windows(windows);
@@ -473,7 +613,7 @@ py::list nq_devpool_chain_py(const py::bytes& nodes, int N, const std::vector<lo
   {
     py::gil_scoped_release rel;
     snaps = nq_devpool_chain(v, N, g, finish, static_cast<unsigned long long>(m), w, cap,
-                             presum, device, split);
+                             presum, device, split, refill);
   }
   return chain_to_list(snaps);
 }
@@ -896,6 +1036,16 @@ PYBIND11_MODULE(_core, mod) {
           py::arg("c2"));
   mod.def("nq_sub_decode", &nq_sub_decode_py, py::arg("entry"));
   mod.def("nq_split_default", &nq_split_default);
+  mod.def("nq_finish_wave_cpu", &nq_finish_wave_cpu, py::arg("jobs"), py::arg("N"),
+          py::arg("g") = 1, py::arg("split") = NQ_SPLIT_DEFAULT,
+          py::arg("qcap") = NQ_SPLIT_QCAP, py::arg("refill") = NQ_REFILL_DEFAULT,
+          py::arg("lanes") = 64, py::arg("waves") = 4);
+  mod.def("nq_pmask_pack", &nq_pmask_pack, py::arg("cols"), py::arg("d1"), py::arg("d2"));
+  mod.def("nq_pmask_unpack", &nq_pmask_unpack_py, py::arg("word"));
+  mod.def("nq_job_ref", &nq_job_ref, py::arg("parent"), py::arg("col"));
+  mod.def("nq_job_state", &nq_job_state_py, py::arg("word"), py::arg("ref"), py::arg("N"));
+  mod.def("nq_refill_default", &nq_refill_default);
+  mod.attr("NQ_REFILL_DEFAULT") = NQ_REFILL_DEFAULT;
   mod.attr("NQ_SPLIT_QCAP") = NQ_SPLIT_QCAP;
   mod.attr("NQ_SPLIT_MAX") = NQ_SPLIT_MAX;
   mod.def("pfsp_cpu_bounds", &pfsp_cpu_bounds);
@@ -937,7 +1087,8 @@ PYBIND11_MODULE(_core, mod) {
   mod.def("nq_devpool_step", &nq_devpool_step_py, py::arg("nodes"), py::arg("N"),
           py::arg("g") = 1, py::arg("finish") = 8, py::arg("m") = 1,
           py::arg("M") = py::none(), py::arg("capacity") = py::none(),
-          py::arg("presum") = "auto", py::arg("device") = 0, py::arg("split") = -1);
+          py::arg("presum") = "auto", py::arg("device") = 0, py::arg("split") = -1,
+          py::arg("refill") = -1);
   mod.def("pfsp_devpool_step", &pfsp_devpool_step_py, py::arg("nodes"), py::arg("inst"),
           py::arg("lb"), py::arg("best"), py::arg("m") = 1, py::arg("M") = py::none(),
           py::arg("capacity") = py::none(), py::arg("geom") = -1,
@@ -945,7 +1096,7 @@ PYBIND11_MODULE(_core, mod) {
   mod.def("nq_devpool_chain", &nq_devpool_chain_py, py::arg("nodes"), py::arg("N"),
           py::arg("windows"), py::arg("g") = 1, py::arg("finish") = 8, py::arg("m") = 1,
           py::arg("capacity") = py::none(), py::arg("presum") = "auto",
-          py::arg("device") = 0, py::arg("split") = -1);
+          py::arg("device") = 0, py::arg("split") = -1, py::arg("refill") = -1);
   mod.def("pfsp_devpool_chain", &pfsp_devpool_chain_py, py::arg("nodes"), py::arg("inst"),
           py::arg("lb"), py::arg("best"), py::arg("windows"), py::arg("m") = 1,
           py::arg("capacity") = py::none(), py::arg("geom") = -1,

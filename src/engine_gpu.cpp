@@ -492,6 +492,18 @@ int nq_split_default() {
   return split;
 }
 
+// GATS_NQ_REFILL: idle lanes (1..64) at which a wave of the split finisher
+// fetches sub-jobs for all of its idle lanes (nq_refill_now); 1 refills as
+// soon as any lane is idle. Read once.
+int nq_refill_default() {
+  static const int refill = [] {
+    int v = NQ_REFILL_DEFAULT;
+    if (const char* e = std::getenv("GATS_NQ_REFILL")) v = atoi(e);
+    return v < 1 ? 1 : v > 64 ? 64 : v;
+  }();
+  return refill;
+}
+
 DevpoolMultiOut nq_devpool_multi(Pool<NQNode>& pool, int N, int g, int m, int M,
                                  const std::vector<int>& devices,
                                  unsigned long long capacity, Result& r) {

@@ -206,11 +206,14 @@ void validate_pfsp_step(const std::vector<PFSPNode>& nodes, int inst, const std:
                         unsigned long long capacity, int geom, const std::string& presum,
                         const std::string& br = "fwd");
 // split: levels the finisher jobs are split (0..2), < 0 = the engine's default
+// refill: idle lanes at which a wave of the split finisher refills (1..64),
+// < 0 = the engine's default
 int nq_split_default();
+int nq_refill_default();
 DevpoolStepCtl nq_devpool_step(std::vector<NQNode>& nodes, int N, int g, int finish,
                                unsigned long long m, unsigned long long M,
                                unsigned long long capacity, const std::string& presum,
-                               int device, int split = -1);
+                               int device, int split = -1, int refill = -1);
 DevpoolStepCtl pfsp_devpool_step(std::vector<PFSPNode>& nodes, int inst, const std::string& lb,
                                  int best, unsigned long long m, unsigned long long M,
                                  unsigned long long capacity, int geom,
@@ -242,7 +245,7 @@ struct DevpoolSnapshot {
 std::vector<DevpoolSnapshot<NQNode>> nq_devpool_chain(
     const std::vector<NQNode>& nodes, int N, int g, int finish, unsigned long long m,
     const std::vector<unsigned long long>& windows, unsigned long long capacity,
-    const std::string& presum, int device, int split = -1);
+    const std::string& presum, int device, int split = -1, int refill = -1);
 std::vector<DevpoolSnapshot<PFSPNode>> pfsp_devpool_chain(
     const std::vector<PFSPNode>& nodes, int inst, const std::string& lb, int best,
     unsigned long long m, const std::vector<unsigned long long>& windows,

@@ -179,17 +179,22 @@ struct NqDevProblem {
   int g;
   int finish;  // depth of the in-thread bitmask subtree finisher
   int split;   // levels the finisher jobs are split into sub-jobs (0..2)
+  int refill;  // idle lanes at which a wave of the split finisher refills (1..64)
 
-  // split < 0: the engine's default (GATS_NQ_SPLIT)
-  NqDevProblem(int N, int g_, int finish_, int split_ = -1)
-      : per(N), g(g_), finish(finish_), split(split_ < 0 ? nq_split_default() : split_) {}
+  // split < 0 / refill < 0: the engine's defaults (GATS_NQ_SPLIT, GATS_NQ_REFILL)
+  NqDevProblem(int N, int g_, int finish_, int split_ = -1, int refill_ = -1)
+      : per(N),
+        g(g_),
+        finish(finish_),
+        split(split_ < 0 ? nq_split_default() : split_),
+        refill(refill_ < 0 ? nq_refill_default() : refill_) {}
   NqDevProblem on_device(int) const { return *this; }
 
   void enqueue(const DevpoolBufs<NQNode>& b, DevCtl* cur, DevCtl* next, unsigned long long m,
                unsigned long long Mi, bool presum, hipStream_t s) const {
     const int Gi = devpool_grid(Mi, per, lbg);
-    launch_nq_x(cur, b.pool.p, b.childbuf.p, b.bc.p, b.bs.p, b.be(), per, g, finish, split, m,
-                Mi, s);
+    launch_nq_x(cur, b.pool.p, b.childbuf.p, b.bc.p, b.bs.p, b.be(), per, g, finish, split,
+                refill, m, Mi, s);
     if (presum) launch_presum(b.bc.p, b.gsum.p, Gi, s);
     launch_gather2_nq(cur, next, b.bc.p, b.bs.p, b.be(), presum ? b.gsum.p : nullptr,
                       b.childbuf.p, b.pool.p, b.stride, Gi, m, Mi, b.capacity, s);

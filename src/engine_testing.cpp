@@ -182,10 +182,11 @@ DevpoolStepCtl devpool_step(const Problem& problem, std::vector<typename Problem
 DevpoolStepCtl nq_devpool_step(std::vector<NQNode>& nodes, int N, int g, int finish,
                                unsigned long long m, unsigned long long M,
                                unsigned long long capacity, const std::string& presum,
-                               int device, int split) {
+                               int device, int split, int refill) {
   validate_nq_step(nodes, N, g, finish, m, M, capacity, presum);  // before any HIP call
   if (split > NQ_SPLIT_MAX) throw std::invalid_argument("split must be in 0..2, or < 0");
-  return devpool_step(NqDevProblem(N, g, finish, split), nodes, /*best=*/0, m, M, capacity,
+  if (refill == 0 || refill > 64) throw std::invalid_argument("refill must be in 1..64, or < 0");
+  return devpool_step(NqDevProblem(N, g, finish, split, refill), nodes, /*best=*/0, m, M, capacity,
                       presum_mode(presum), device);
 }
 
@@ -308,11 +309,12 @@ std::vector<DevpoolSnapshot<typename Problem::Node>> devpool_chain(
 std::vector<DevpoolSnapshot<NQNode>> nq_devpool_chain(
     const std::vector<NQNode>& nodes, int N, int g, int finish, unsigned long long m,
     const std::vector<unsigned long long>& windows, unsigned long long capacity,
-    const std::string& presum, int device, int split) {
+    const std::string& presum, int device, int split, int refill) {
   validate_nq_step(nodes, N, g, finish, m, 1, capacity, presum);  // before any HIP call
   if (split > NQ_SPLIT_MAX) throw std::invalid_argument("split must be in 0..2, or < 0");
+  if (refill == 0 || refill > 64) throw std::invalid_argument("refill must be in 1..64, or < 0");
   validate_chain_windows(windows, N, capacity);
-  return devpool_chain(NqDevProblem(N, g, finish, split), nodes, /*best=*/0, m, windows, capacity,
+  return devpool_chain(NqDevProblem(N, g, finish, split, refill), nodes, /*best=*/0, m, windows, capacity,
                        presum_mode(presum), device);
 }
 

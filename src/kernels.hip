@@ -678,16 +678,17 @@ __device__ inline unsigned long long derive_chunk(const DevCtl* ctl, unsigned lo
 // ... SPLIT == 1 / 2: every job is first split one / two levels into sub-jobs
 // (nq_finish.hpp), the sub-jobs go into a second LDS queue of NQ_SPLIT_QCAP
 // entries (ranked by a block scan, filled and drained in rounds when they do
-// not all fit), and a lane that finishes one takes the next unclaimed entry
-// from an LDS counter: which lane walks what varies, the sums do not.
+// not all fit), and a wave that has `refill` idle lanes (or only idle lanes)
+// hands all of them the next unclaimed entries from an LDS counter
+// (nq_refill_now): which lane walks what varies, the sums do not.
 template <bool G1, int SPLIT>
 __global__ void k_nq_x(const DevCtl* ctl, const NQNode* pool, NQNode* childbuf,
                        uint32_t* blockCounts, unsigned long long* blockSols,
-                       unsigned long long* blockExtra, int N, int g, int finish,
+                       unsigned long long* blockExtra, int N, int g, int finish, int refill,
                        unsigned long long m, unsigned long long M) {
   __shared__ NQNode s[EMIT_TILE / 4 + 2];  // N >= 4 (engine falls back below)
-  __shared__ uint32_t pmask[EMIT_TILE / 4 + 2][3];  // per-parent cols/d1/d2
-  __shared__ uint16_t jobq[EMIT_TILE];  // finisher jobs: local parent id * 32 + k
+  __shared__ uint64_t pmask[EMIT_TILE / 4 + 2];  // per-parent cols/d1/d2 (nq_pmask_pack)
+  __shared__ uint16_t jobq[EMIT_TILE];  // finisher jobs: nq_job_ref(local parent id, column)
   __shared__ uint32_t jobcnt[(EMIT_TILE / BLOCK) * (BLOCK / 64)];  // jobs per (j, wave)
   const unsigned long long c = derive_chunk(ctl, m, M);
   // child indices fit u32: the engine enforces M * branching <= 2^31
@@ -700,6 +701,7 @@ __global__ void k_nq_x(const DevCtl* ctl, const NQNode* pool, NQNode* childbuf,
   uint8_t lab[EMIT_TILE / BLOCK] = {0, 0, 0, 0};  // 1 = pushed child, 2 = finisher job
   uint16_t lpid[EMIT_TILE / BLOCK];
   uint8_t lk[EMIT_TILE / BLOCK];
+  uint8_t lcol[EMIT_TILE / BLOCK] = {0, 0, 0, 0};  // the slot's column (job slots)
   if (c0 < total) {
     const uint32_t msk = (1u << N) - 1u;
     uint32_t c1 = c0 + EMIT_TILE;
@@ -718,9 +720,7 @@ __global__ void k_nq_x(const DevCtl* ctl, const NQNode* pool, NQNode* childbuf,
           d1 = ((d1 | b) << 1) & msk;
           d2 = (d2 | b) >> 1;
         }
-        pmask[pi][0] = cols;
-        pmask[pi][1] = d1;
-        pmask[pi][2] = d2;
+        pmask[pi] = nq_pmask_pack(cols, d1, d2);
       }
     }
     __syncthreads();
@@ -737,9 +737,11 @@ __global__ void k_nq_x(const DevCtl* ctl, const NQNode* pool, NQNode* childbuf,
         if (depth == N) {
           sols += (k == 0);  // leaf parent counted once (nqueens_chpl.chpl:78-80)
         } else if (k >= depth) {
-          const uint32_t* pm = pmask[pid - first];
-          const uint32_t occ = pm[0] | pm[1] | pm[2];
-          const uint32_t b = 1u << p.board[k];
+          uint32_t pc, pd1, pd2;
+          nq_pmask_unpack(pmask[pid - first], pc, pd1, pd2);
+          const uint32_t occ = pc | pd1 | pd2;
+          lcol[j] = p.board[k];
+          const uint32_t b = 1u << lcol[j];
           const uint32_t freemask = G1 ? (~occ & msk) : nq_free_occ_g(occ, msk, g);
           if (b & freemask) {  // == nq_safe (diagonal masks)
             const int rem = N - (depth + 1);  // levels below the child
@@ -777,23 +779,17 @@ __global__ void k_nq_x(const DevCtl* ctl, const NQNode* pool, NQNode* childbuf,
     }
 #pragma unroll
     for (int j = 0; j < EMIT_TILE / BLOCK; j++)
-      if (lab[j] == 2) jobq[rank[j]] = static_cast<uint16_t>(lpid[j] * 32u + lk[j]);
+      if (lab[j] == 2) jobq[rank[j]] = static_cast<uint16_t>(nq_job_ref(lpid[j], lcol[j]));
     __syncthreads();
     // phase C: one flat loop per lane over its share of the queue
     static_assert(MAX_JOBS <= 32 && (EMIT_TILE / 4 + 2) * 32 <= 65536, "jobq entry is 16-bit");
     NqFlat<NQ_FLAT_LEVELS_DEV> st;
     st.tree = 0;
     st.sol = 0;
-    // job ref (local parent id * 32 + k) -> the child's masks, seen from the
-    // row below it (as phase A steps them); returns that row
+    // job ref -> the child's masks, seen from the row below it (as phase A
+    // steps them); returns that row. One LDS read: the parent's packed masks.
     auto job_state = [&](uint32_t e, uint32_t& jc, uint32_t& jd1, uint32_t& jd2) {
-      const uint32_t pi = e >> 5;
-      const NQNode& p = s[pi];
-      jc = pmask[pi][0];
-      jd1 = pmask[pi][1];
-      jd2 = pmask[pi][2];
-      nq_step_down(jc, jd1, jd2, 1u << p.board[e & 31u], msk);
-      return static_cast<int>(p.depth) + 1;
+      return nq_job_state(pmask[nq_job_parent(e)], e, msk, jc, jd1, jd2);
     };
     if constexpr (SPLIT == 0) {
       uint32_t q = threadIdx.x;
@@ -836,9 +832,18 @@ __global__ void k_nq_x(const DevCtl* ctl, const NQNode* pool, NQNode* childbuf,
       if (threadIdx.x == 0) joboff[njobs] = static_cast<uint16_t>(run);
       __syncthreads();
       // phase C2, rounds: the longest run of jobs whose sub-jobs fit the queue
-      // is written out and drained; a lane that finishes a sub-job takes the
-      // next unclaimed entry (one LDS add per wave and fetch).
+      // is written out and drained. A wave refills all of its idle lanes at
+      // once when `refill` of them are idle (nq_refill_now: one LDS add per
+      // refill, two LDS reads per lane); otherwise a scalar branch skips the
+      // fetch.
+      static_assert(sizeof(s) + sizeof(pmask) + sizeof(jobq) + sizeof(jobcnt) + sizeof(joboff) +
+                            sizeof(subq) + sizeof(qhead) + 4 * sizeof(uint32_t) +
+                            4 * sizeof(unsigned long long) + 16 <=
+                        20480,
+                    "k_nq_x's LDS (with the scan / reduce scratch and padding) must leave "
+                    "eight blocks per CU");
       const unsigned long long lt = (1ull << lane) - 1ull;
+      const uint32_t T = static_cast<uint32_t>(refill);
       for (uint32_t jb = 0; jb < njobs;) {  // block-uniform: je comes from LDS alone
         const uint32_t je = nq_round_end(joboff, jb, njobs, NQ_SPLIT_QCAP);
         const uint32_t base = joboff[jb];
@@ -855,24 +860,40 @@ __global__ void k_nq_x(const DevCtl* ctl, const NQNode* pool, NQNode* childbuf,
         }
         if (threadIdx.x == 0) qhead = 0;
         __syncthreads();
-        nq_flat_run<NQ_FLAT_LEVELS_DEV, G1>(
-            st,
-            [&](NqFlat<NQ_FLAT_LEVELS_DEV>& w) {
-              // the lanes that ask together (EXEC is partial here) share one add
-              const unsigned long long ask = __ballot(1);
-              const uint32_t rank = static_cast<uint32_t>(__popcll(ask & lt));
-              uint32_t got = 0;
-              if (rank == 0) got = atomicAdd(&qhead, static_cast<uint32_t>(__popcll(ask)));
-              got = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(got)));
-              const uint32_t qi = got + rank;
-              if (qi >= nsub) return false;
-              const uint32_t e = subq[qi];
-              uint32_t jc, jd1, jd2;
-              const int row = job_state(nq_sub_ref(e), jc, jd1, jd2);
-              nq_sub_load<G1>(w, e, jc, jd1, jd2, row, N, msk, g);
-              return true;
-            },
-            msk, g);
+        // Every lane of the wave stays in the loop until the wave leaves it
+        // (the ballots need them all): `drained`, the refill decision and the
+        // exit are wave-uniform. Why it ends: see nq_refill_now (nq_finish.hpp).
+        // The iterations that only step are an inner loop of their own: one
+        // ballot, one scalar compare against nq_refill_level, no fetch code.
+        bool drained = false;
+        st.cand = 0;
+        st.stack = 0;
+        bool idle = true;                  // every lane starts without a walk,
+        unsigned long long im = ~0ull;     // so the all-idle rule starts the wave
+        uint32_t nidle = 64u;
+        for (;;) {
+          if (nq_wave_done(nidle, 64u, drained)) break;
+          // here nq_refill_now(nidle, 64, T, drained) holds
+          uint32_t got = 0;
+          if (lane == 0) got = atomicAdd(&qhead, nidle);
+          got = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(got)));
+          drained = nq_refill_drains(got, nidle, nsub);
+          const uint32_t qi = got + static_cast<uint32_t>(__popcll(im & lt));
+          if (idle && qi < nsub) {  // qi < nsub <= NQ_SPLIT_QCAP: inside subq
+            const uint32_t e = subq[qi];
+            uint32_t jc, jd1, jd2;
+            const int row = job_state(nq_sub_ref(e), jc, jd1, jd2);
+            nq_sub_load<G1>(st, e, jc, jd1, jd2, row, N, msk, g);
+          }
+          const uint32_t level = nq_refill_level(64u, T, drained);
+          do {
+            if (st.cand == 0 && st.stack > 1) st.pop(msk);
+            if (st.cand) st.template take<G1>(msk, g);
+            idle = nq_lane_idle(st.cand, st.stack);
+            im = __builtin_amdgcn_ballot_w64(idle);
+            nidle = static_cast<uint32_t>(__popcll(im));
+          } while (nidle < level);
+        }
         __syncthreads();  // the next round rewrites subq and qhead
         jb = je;
       }
@@ -1838,10 +1859,11 @@ int devpool_stride(int lbk) {
 void launch_nq_x(const DevCtl* ctl, const NQNode* pool, NQNode* childbuf,
                  uint32_t* blockCounts, unsigned long long* blockSols,
                  unsigned long long* blockExtra, int N, int g, int finish, int split,
-                 unsigned long long m, unsigned long long M, hipStream_t s) {
+                 int refill, unsigned long long m, unsigned long long M, hipStream_t s) {
+  refill = refill < 1 ? 1 : refill > 64 ? 64 : refill;  // idle lanes of a 64-lane wave
   auto go = [&](auto kernel) {
     hipLaunchKernelGGL(kernel, dim3(devpool_grid(M, N, 1)), dim3(BLOCK), 0, s, ctl, pool,
-                       childbuf, blockCounts, blockSols, blockExtra, N, g, finish, m, M);
+                       childbuf, blockCounts, blockSols, blockExtra, N, g, finish, refill, m, M);
   };
   if (g == 1)
     split <= 0 ? go(k_nq_x<true, 0>) : split == 1 ? go(k_nq_x<true, 1>) : go(k_nq_x<true, 2>);

@@ -178,12 +178,15 @@ NQ_HD inline void nq_flat_run(NqFlat<LEVELS>& st, Next&& next, uint32_t msk, int
 // job whole. A sub-job's root may be the bottom row; NqFlat::load counts it.
 // ---------------------------------------------------------------------------
 
-// Queue capacity: the largest that keeps k_nq_x's LDS (11,456 B + 2,052 B of
-// offsets + the queue) within 20,480 B, i.e. eight blocks per CU; 2048 entries
-// need fewer second rounds but leave seven blocks and measured slower
-// (BASELINE.md "Split finisher jobs"). -DGATS_NQ_QCAP=n builds another size.
+// Queue capacity: k_nq_x's LDS (10,424 B + 2,052 B of offsets + the queue) has
+// to stay within 20,480 B, i.e. eight blocks per CU (a static_assert in the
+// kernel, which 1996 entries, 20,464 B, are the largest multiple of four to
+// pass); 2048 entries need fewer second rounds but leave seven blocks and
+// measured slower (BASELINE.md "Split finisher jobs"), 1728 (the capacity
+// before pmask was packed) 0.17 ms slower (BASELINE.md "Batched refill").
+// -DGATS_NQ_QCAP=n builds another size.
 #ifndef GATS_NQ_QCAP
-#define GATS_NQ_QCAP 1728
+#define GATS_NQ_QCAP 1996
 #endif
 inline constexpr int NQ_SPLIT_MAX = 2;                // deepest split
 inline constexpr int NQ_SPLIT_DEFAULT = 2;            // GATS_NQ_SPLIT's default
@@ -261,6 +264,69 @@ NQ_HD inline void nq_sub_load(NqFlat<LEVELS>& w, uint32_t e, uint32_t c, uint32_
   if (nc >= 2) nq_step_down(c, d1, d2, 1u << nq_sub_c2(e), msk);
   w.template load<G1>(c, d1, d2, row + static_cast<int>(nc), N, msk, g);
 }
+
+// A parent's three masks in one 64-bit word (one LDS read): N <= 20, so each
+// of cols / d1 / d2 is below 2^20.
+inline constexpr int NQ_PMASK_BITS = 20;
+NQ_HD inline uint64_t nq_pmask_pack(uint32_t cols, uint32_t d1, uint32_t d2) {
+  return static_cast<uint64_t>(cols) | static_cast<uint64_t>(d1) << NQ_PMASK_BITS |
+         static_cast<uint64_t>(d2) << (2 * NQ_PMASK_BITS);
+}
+NQ_HD inline void nq_pmask_unpack(uint64_t w, uint32_t& cols, uint32_t& d1, uint32_t& d2) {
+  constexpr uint32_t m = (1u << NQ_PMASK_BITS) - 1u;
+  cols = static_cast<uint32_t>(w) & m;
+  d1 = static_cast<uint32_t>(w >> NQ_PMASK_BITS) & m;
+  d2 = static_cast<uint32_t>(w >> (2 * NQ_PMASK_BITS)) & m;
+}
+
+// Job reference: local parent id * 32 + the child's COLUMN (not its slot), so
+// the job's state comes from the parent's packed masks alone: the child's
+// masks seen from the row below it, and that row. The parent's depth is
+// popcount(cols): its board prefix is part of a permutation, so every placed
+// queen has a column of its own.
+NQ_HD inline uint32_t nq_job_ref(uint32_t parent, uint32_t col) { return parent * 32u + col; }
+NQ_HD inline uint32_t nq_job_parent(uint32_t ref) { return ref >> 5; }
+NQ_HD inline int nq_job_state(uint64_t pm, uint32_t ref, uint32_t msk, uint32_t& c, uint32_t& d1,
+                              uint32_t& d2) {
+  nq_pmask_unpack(pm, c, d1, d2);
+  const int row = __builtin_popcount(c) + 1;
+  nq_step_down(c, d1, d2, 1u << (ref & 31u), msk);
+  return row;
+}
+
+// The drain's refill rule, per wave (k_nq_x SPLIT >= 1 and nq_finish_wave_cpu).
+// A lane is idle when it has no walk (cand == 0 && stack <= 1). In every
+// iteration the wave counts its idle lanes; it fetches, for all of them at
+// once, when it is not drained and at least `T` of its `lanes` lanes are idle,
+// or all of them are (so fewer than T entries still get started). A wave whose
+// allotment [got, got + nidle) reaches the end of the round's queue is drained:
+// it asks no more, runs its remaining walks to the end, and leaves when every
+// lane is idle. Both results depend on wave-uniform values only.
+//
+// The loop ends: (1) a refill (nidle >= 1) hands out at least one entry or sets
+// drained: unless got + nidle >= nsub, all nidle entries exist; (2) once a wave
+// is drained no idle lane becomes active again, since only a refill loads a
+// lane; (3) every step of an active lane advances its walk (a take consumes a
+// candidate, a pop shortens the stack, and a walk is finite). A wave that is
+// not drained and has no active lane refills (all-idle rule), so between two
+// refills of a wave at least one lane steps; (1) bounds the refills by the
+// queue's length + 1, (3) the steps.
+NQ_HD inline bool nq_lane_idle(uint32_t cand, uint64_t stack) { return cand == 0 && stack <= 1; }
+// The idle-lane count at which the wave acts: it refills, or leaves once it is
+// drained. Below it the wave only steps (the kernel's inner loop).
+NQ_HD inline uint32_t nq_refill_level(uint32_t lanes, uint32_t T, bool drained) {
+  return drained || T > lanes ? lanes : T;
+}
+NQ_HD inline bool nq_refill_now(uint32_t nidle, uint32_t lanes, uint32_t T, bool drained) {
+  return !drained && nidle != 0 && nidle >= nq_refill_level(lanes, T, false);
+}
+NQ_HD inline bool nq_wave_done(uint32_t nidle, uint32_t lanes, bool drained) {
+  return drained && nidle >= nq_refill_level(lanes, lanes, true);
+}
+NQ_HD inline bool nq_refill_drains(uint32_t got, uint32_t nidle, uint32_t nsub) {
+  return got + nidle >= nsub;
+}
+inline constexpr int NQ_REFILL_DEFAULT = 24;  // GATS_NQ_REFILL's default
 
 // Rounds cut. off[0..njobs] are the jobs' exclusive sub-job offsets in queue
 // order (off[njobs] = all of them). A round takes the longest run of jobs
