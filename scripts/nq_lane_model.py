@@ -19,7 +19,15 @@ What the model leaves out, and what the measurement showed it matters
 executes them whenever ANY of its lanes fetches, so with five sub-jobs per
 lane nearly every iteration of a wave carries a fetch for one or two lanes.
 
-usage: nq_lane_model.py [--tiles 24] [--seed 1] [--N 17]
+The wave-stack schedule (nq_stack_act and friends) is played as well: a lane
+owns a row and takes one candidate per iteration, children with an inner row
+below them go onto the wave's stack, idle lanes take entries off it or draw
+jobs. Reported: wave iterations, lane efficiency, fetch passes, the longest
+wave, and the peak stack height per wave, from which NQ_STACK_CAP is chosen;
+with --cap the pushes stop at sp + 64 > cap as in the kernel and the children
+walked instead are counted (their walk's iterations are charged to the wave).
+
+usage: nq_lane_model.py [--tiles 24] [--seed 1] [--N 17] [--cap 312]
 """
 import argparse
 import heapq
@@ -192,11 +200,101 @@ def schedule_waves(jobs, N, S, T, qcap):
     return work, iters, fetches
 
 
+def run_stack(jobs, N, T, shared=True, cap=None, fair=True, nwaves=LANES // WAVE):
+    """The wave-stack finisher on one tile. shared: idle lanes draw jobs from
+    one counter, at most the wave's even share per refill when `fair` (the
+    kernel's rule, nq_stack_draw), else one per idle lane; otherwise the jobs are dealt round-robin
+    onto the waves' stacks in advance. cap None: unbounded stacks. Returns
+    (takes, iterations summed over the waves, fetch passes, longest wave,
+    peak stack of a wave, children walked by the fallback)."""
+    msk = (1 << N) - 1
+    stk = [[] for _ in range(nwaves)]
+    queue = list(jobs) if shared else []
+    if not shared:
+        for q, (c, d1, d2, row) in enumerate(jobs):
+            stk[q % nwaves].append((c, d1, d2, N - 1 - row))
+    head = 0
+    rows = [[None] * WAVE for _ in range(nwaves)]  # [c, d1, d2, h, cand] or None
+    more = [shared] * nwaves
+    its = [0] * nwaves
+    takes = fetches = peak = walked = 0
+    clock = [(0, w) for w in range(nwaves)]
+    while clock:
+        t, w = heapq.heappop(clock)
+        lanes, st = rows[w], stk[w]
+        idle = [i for i, r in enumerate(lanes) if r is None]
+        if len(idle) == WAVE or ((st or more[w]) and len(idle) >= T):
+            if len(idle) == WAVE and not st and not more[w]:
+                continue  # the wave leaves
+            fetches += 1
+            share = max(1, -(-len(queue) // nwaves)) if fair else WAVE  # nq_stack_draw
+            for i in idle:
+                if st:
+                    c, d1, d2, h = st.pop()
+                elif more[w]:
+                    if head >= len(queue) or share == 0:
+                        break
+                    share -= 1
+                    c, d1, d2, row = queue[head]
+                    head += 1
+                    h = N - 1 - row
+                else:
+                    break
+                cand = free_of(c, d1, d2, msk)
+                if cand and h:
+                    lanes[i] = [c, d1, d2, h, cand]
+            if more[w] and head >= len(queue):
+                more[w] = False
+        can = cap is None or len(st) + WAVE <= cap
+        extra = 0
+        for i, r in enumerate(lanes):
+            if r is None:
+                continue
+            c, d1, d2, h, cand = r
+            bit = cand & -cand
+            r[4] = cand ^ bit
+            takes += 1
+            if h > 1:
+                n = down(c, d1, d2, bit, msk)
+                if free_of(*n, msk):
+                    if can:
+                        st.append(n + (h - 1,))
+                    else:  # the lane walks the child; the whole wave waits
+                        walked += 1
+                        extra = max(extra, flat_iters(*n, N - h, N) - 1)
+            if r[4] == 0:
+                lanes[i] = None
+        peak = max(peak, len(st))
+        its[w] += 1 + extra
+        heapq.heappush(clock, (t + 1 + extra, w))
+    return takes, sum(its), fetches, max(its), peak, walked
+
+
+def stack_table(tiles, N, cap):
+    print()
+    print("wave stack, four waves; refill when >= T lanes are idle (per tile; peak over all tiles)")
+    print(f"{'seeds':>8s} {'cap':>5s} {'T':>3s} {'wave iters':>10s} {'lane eff.':>9s} "
+          f"{'fetches':>8s} {'longest':>8s} {'peak sp':>8s} {'walked':>7s}")
+    for shared, fair in ((True, True), (True, False), (False, False)):
+        for c in (None, cap):
+            for T in (1, 8, 16, 24):
+                tk = it = fe = lo = wk = pk = 0
+                for jobs in tiles:
+                    a = run_stack(jobs, N, T, shared, c, fair)
+                    tk, it, fe, lo, wk = tk + a[0], it + a[1], fe + a[2], lo + a[3], wk + a[5]
+                    pk = max(pk, a[4])
+                n = len(tiles)
+                seeds = ('share' if fair else 'queue') if shared else 'dealt'
+                print(f"{seeds:>8s} {c or 'inf':>5} {T:3d} {it / n:10.0f} "
+                      f"{tk / (it * WAVE):9.2f} {fe / n:8.0f} {lo / n:8.0f} {pk:8d} {wk / n:7.0f}")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--tiles", type=int, default=24)
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--N", type=int, default=17)
+    ap.add_argument("--cap", type=int, default=312, help="wave-stack capacity [entries]")
     a = ap.parse_args()
     rng = random.Random(a.seed)
     tiles = [sample_tile(rng, a.N) for _ in range(a.tiles)]
@@ -236,6 +334,7 @@ def main():
             work, iters, fetches = work + w, iters + i, fetches + f
         print(f"{T:4d} {fetches / a.tiles:11.0f} {work / (iters * WAVE):9.2f} " +
               " ".join(f"{(iters + (f - 1) * fetches) / a.tiles:11.0f}" for f in fs))
+    stack_table(tiles, a.N, a.cap)
 
 
 if __name__ == "__main__":

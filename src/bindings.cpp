@@ -12,6 +12,7 @@
 #include "gpu_api.hpp"
 #include "nodes.hpp"
 #include "nq_finish.hpp"
+#include "nq_finish_stack_cpu.hpp"
 #include "pool.hpp"
 #include "search_host.hpp"
 #include "share_selftest.hpp"
@@ -293,6 +294,20 @@ py::tuple nq_finish_wave_cpu(const std::vector<std::array<uint32_t, 4>>& jobs, i
                 : nq_finish_wave<false>(jobs, N, g, split, q, T, L, W);
 }
 
+// CPU run of k_nq_x's wave-stack finisher for one block (nq_finish_stack_cpu.hpp).
+// Returns (tree, sol, iterations per wave, peak sp per wave, fallback walks).
+py::tuple nq_finish_stack_cpu(const std::vector<std::array<uint32_t, 4>>& jobs, int N, int g,
+                              int refill, int waves, int lanes, long long cap) {
+  const NqStackRun r = nq_finish_stack(jobs, N, g, refill, waves, lanes, cap);
+  return py::make_tuple(r.tree, r.sol, r.iters, r.peak_sp, r.fallbacks);
+}
+
+py::tuple nq_entry_unpack_py(uint64_t w) {
+  uint32_t c, d1, d2;
+  const uint32_t h = nq_entry_unpack(w, c, d1, d2);
+  return py::make_tuple(c, d1, d2, h);
+}
+
 // The packed parent masks and the job reference, for tests.
 py::tuple nq_pmask_unpack_py(uint64_t w) {
   uint32_t c, d1, d2;
@@ -550,7 +565,8 @@ py::dict step_ctl_to_dict(const DevpoolStepCtl& c) {
 
 py::tuple nq_devpool_step_py(const py::bytes& nodes, int N, int g, int finish, long long m,
                              const py::object& M, const py::object& capacity,
-                             const std::string& presum, int device, int split, int refill) {
+                             const std::string& presum, int device, int split, int refill,
+                             int stack, int stack_cap) {
   auto v = nodes_from_bytes<NQNode>(nodes);
   if (m < 0) throw std::invalid_argument("m must be >= 1");
   const unsigned long long Mv = step_arg(M, v.empty() ? 1 : v.size(), "M");
@@ -559,7 +575,7 @@ py::tuple nq_devpool_step_py(const py::bytes& nodes, int N, int g, int finish, l
   {
     py::gil_scoped_release rel;
     c = nq_devpool_step(v, N, g, finish, static_cast<unsigned long long>(m), Mv, cap, presum,
-                        device, split, refill);
+                        device, split, refill, stack, stack_cap);
   }
   return py::make_tuple(nodes_to_bytes(v.data(), v.size()), step_ctl_to_dict(c));
 }
@@ -604,7 +620,8 @@ py::list chain_to_list(const std::vector<DevpoolSnapshot<NodeT>>& snaps) {
 
 py::list nq_devpool_chain_py(const py::bytes& nodes, int N, const std::vector<long long>& windows,
                              int g, int finish, long long m, const py::object& capacity,
-                             const std::string& presum, int device, int split, int refill) {
+                             const std::string& presum, int device, int split, int refill,
+                             int stack, int stack_cap) {
   auto v = nodes_from_bytes<NQNode>(nodes);
   if (m < 0) throw std::invalid_argument("m must be >= 1");
   const auto w = chain_windows(windows);
@@ -613,7 +630,7 @@ py::list nq_devpool_chain_py(const py::bytes& nodes, int N, const std::vector<lo
   {
     py::gil_scoped_release rel;
     snaps = nq_devpool_chain(v, N, g, finish, static_cast<unsigned long long>(m), w, cap,
-                             presum, device, split, refill);
+                             presum, device, split, refill, stack, stack_cap);
   }
   return chain_to_list(snaps);
 }
@@ -1044,6 +1061,14 @@ PYBIND11_MODULE(_core, mod) {
   mod.def("nq_pmask_unpack", &nq_pmask_unpack_py, py::arg("word"));
   mod.def("nq_job_ref", &nq_job_ref, py::arg("parent"), py::arg("col"));
   mod.def("nq_job_state", &nq_job_state_py, py::arg("word"), py::arg("ref"), py::arg("N"));
+  mod.def("nq_finish_stack_cpu", &nq_finish_stack_cpu, py::arg("jobs"), py::arg("N"),
+          py::arg("g") = 1, py::arg("refill") = NQ_REFILL_DEFAULT, py::arg("waves") = 4,
+          py::arg("lanes") = 64, py::arg("cap") = NQ_STACK_CAP);
+  mod.def("nq_entry_pack", &nq_entry_pack, py::arg("cols"), py::arg("d1"), py::arg("d2"),
+          py::arg("h"));
+  mod.def("nq_entry_unpack", &nq_entry_unpack_py, py::arg("word"));
+  mod.def("nq_stack_default", &nq_stack_default);
+  mod.attr("NQ_STACK_CAP") = NQ_STACK_CAP;
   mod.def("nq_refill_default", &nq_refill_default);
   mod.attr("NQ_REFILL_DEFAULT") = NQ_REFILL_DEFAULT;
   mod.attr("NQ_SPLIT_QCAP") = NQ_SPLIT_QCAP;
@@ -1088,7 +1113,7 @@ PYBIND11_MODULE(_core, mod) {
           py::arg("g") = 1, py::arg("finish") = 8, py::arg("m") = 1,
           py::arg("M") = py::none(), py::arg("capacity") = py::none(),
           py::arg("presum") = "auto", py::arg("device") = 0, py::arg("split") = -1,
-          py::arg("refill") = -1);
+          py::arg("refill") = -1, py::arg("stack") = -1, py::arg("stack_cap") = -1);
   mod.def("pfsp_devpool_step", &pfsp_devpool_step_py, py::arg("nodes"), py::arg("inst"),
           py::arg("lb"), py::arg("best"), py::arg("m") = 1, py::arg("M") = py::none(),
           py::arg("capacity") = py::none(), py::arg("geom") = -1,
@@ -1096,7 +1121,8 @@ PYBIND11_MODULE(_core, mod) {
   mod.def("nq_devpool_chain", &nq_devpool_chain_py, py::arg("nodes"), py::arg("N"),
           py::arg("windows"), py::arg("g") = 1, py::arg("finish") = 8, py::arg("m") = 1,
           py::arg("capacity") = py::none(), py::arg("presum") = "auto",
-          py::arg("device") = 0, py::arg("split") = -1, py::arg("refill") = -1);
+          py::arg("device") = 0, py::arg("split") = -1, py::arg("refill") = -1,
+          py::arg("stack") = -1, py::arg("stack_cap") = -1);
   mod.def("pfsp_devpool_chain", &pfsp_devpool_chain_py, py::arg("nodes"), py::arg("inst"),
           py::arg("lb"), py::arg("best"), py::arg("windows"), py::arg("m") = 1,
           py::arg("capacity") = py::none(), py::arg("geom") = -1,

@@ -504,6 +504,18 @@ int nq_refill_default() {
   return refill;
 }
 
+// GATS_NQ_STACK: 1 = k_nq_x finishes subtrees from per-wave LDS node stacks
+// (nq_finish.hpp) wherever the split is the default too and g == 1, 0 = the
+// split finisher. Read once.
+int nq_stack_default() {
+  static const int stack = [] {
+    int v = NQ_STACK_DEFAULT;
+    if (const char* e = std::getenv("GATS_NQ_STACK")) v = atoi(e);
+    return v != 0 ? 1 : 0;
+  }();
+  return stack;
+}
+
 DevpoolMultiOut nq_devpool_multi(Pool<NQNode>& pool, int N, int g, int m, int M,
                                  const std::vector<int>& devices,
                                  unsigned long long capacity, Result& r) {

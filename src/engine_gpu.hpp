@@ -208,12 +208,18 @@ void validate_pfsp_step(const std::vector<PFSPNode>& nodes, int inst, const std:
 // split: levels the finisher jobs are split (0..2), < 0 = the engine's default
 // refill: idle lanes at which a wave of the split finisher refills (1..64),
 // < 0 = the engine's default
+// stack: 1 = the wave-stack finisher, 0 = the split one, < 0 = the engine's
+// rule: the stack finisher where split < 0 too, g == 1 and nq_stack_default() is 1
+// stack_cap: the stack height per wave past which children are walked instead
+// of pushed (0..NQ_STACK_CAP), < 0 = NQ_STACK_CAP
 int nq_split_default();
 int nq_refill_default();
+int nq_stack_default();
 DevpoolStepCtl nq_devpool_step(std::vector<NQNode>& nodes, int N, int g, int finish,
                                unsigned long long m, unsigned long long M,
                                unsigned long long capacity, const std::string& presum,
-                               int device, int split = -1, int refill = -1);
+                               int device, int split = -1, int refill = -1, int stack = -1,
+                               int stack_cap = -1);
 DevpoolStepCtl pfsp_devpool_step(std::vector<PFSPNode>& nodes, int inst, const std::string& lb,
                                  int best, unsigned long long m, unsigned long long M,
                                  unsigned long long capacity, int geom,
@@ -245,7 +251,8 @@ struct DevpoolSnapshot {
 std::vector<DevpoolSnapshot<NQNode>> nq_devpool_chain(
     const std::vector<NQNode>& nodes, int N, int g, int finish, unsigned long long m,
     const std::vector<unsigned long long>& windows, unsigned long long capacity,
-    const std::string& presum, int device, int split = -1, int refill = -1);
+    const std::string& presum, int device, int split = -1, int refill = -1, int stack = -1,
+    int stack_cap = -1);
 std::vector<DevpoolSnapshot<PFSPNode>> pfsp_devpool_chain(
     const std::vector<PFSPNode>& nodes, int inst, const std::string& lb, int best,
     unsigned long long m, const std::vector<unsigned long long>& windows,

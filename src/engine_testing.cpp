@@ -179,15 +179,26 @@ DevpoolStepCtl devpool_step(const Problem& problem, std::vector<typename Problem
 
 }  // namespace
 
+// stack = 1 is the finisher of the default split only; stack_cap is its knob
+static void validate_nq_stack(int split, int stack, int stack_cap) {
+  if (stack > 1) throw std::invalid_argument("stack must be 0 or 1, or < 0");
+  if (stack == 1 && split >= 0)
+    throw std::invalid_argument("stack = 1 takes no explicit split");
+  if (stack_cap > NQ_STACK_CAP)
+    throw std::invalid_argument("stack_cap must be in 0.." + std::to_string(NQ_STACK_CAP) +
+                                ", or < 0");
+}
+
 DevpoolStepCtl nq_devpool_step(std::vector<NQNode>& nodes, int N, int g, int finish,
                                unsigned long long m, unsigned long long M,
                                unsigned long long capacity, const std::string& presum,
-                               int device, int split, int refill) {
+                               int device, int split, int refill, int stack, int stack_cap) {
   validate_nq_step(nodes, N, g, finish, m, M, capacity, presum);  // before any HIP call
   if (split > NQ_SPLIT_MAX) throw std::invalid_argument("split must be in 0..2, or < 0");
   if (refill == 0 || refill > 64) throw std::invalid_argument("refill must be in 1..64, or < 0");
-  return devpool_step(NqDevProblem(N, g, finish, split, refill), nodes, /*best=*/0, m, M, capacity,
-                      presum_mode(presum), device);
+  validate_nq_stack(split, stack, stack_cap);
+  return devpool_step(NqDevProblem(N, g, finish, split, refill, stack, stack_cap), nodes,
+                      /*best=*/0, m, M, capacity, presum_mode(presum), device);
 }
 
 DevpoolStepCtl pfsp_devpool_step(std::vector<PFSPNode>& nodes, int inst, const std::string& lb,
@@ -309,13 +320,14 @@ std::vector<DevpoolSnapshot<typename Problem::Node>> devpool_chain(
 std::vector<DevpoolSnapshot<NQNode>> nq_devpool_chain(
     const std::vector<NQNode>& nodes, int N, int g, int finish, unsigned long long m,
     const std::vector<unsigned long long>& windows, unsigned long long capacity,
-    const std::string& presum, int device, int split, int refill) {
+    const std::string& presum, int device, int split, int refill, int stack, int stack_cap) {
   validate_nq_step(nodes, N, g, finish, m, 1, capacity, presum);  // before any HIP call
   if (split > NQ_SPLIT_MAX) throw std::invalid_argument("split must be in 0..2, or < 0");
   if (refill == 0 || refill > 64) throw std::invalid_argument("refill must be in 1..64, or < 0");
+  validate_nq_stack(split, stack, stack_cap);
   validate_chain_windows(windows, N, capacity);
-  return devpool_chain(NqDevProblem(N, g, finish, split, refill), nodes, /*best=*/0, m, windows, capacity,
-                       presum_mode(presum), device);
+  return devpool_chain(NqDevProblem(N, g, finish, split, refill, stack, stack_cap), nodes,
+                       /*best=*/0, m, windows, capacity, presum_mode(presum), device);
 }
 
 std::vector<DevpoolSnapshot<PFSPNode>> pfsp_devpool_chain(

@@ -84,7 +84,8 @@ int devpool_stride(int lbk);
 void launch_nq_x(const DevCtl* ctl, const NQNode* pool, NQNode* childbuf,
                  uint32_t* blockCounts, unsigned long long* blockSols,
                  unsigned long long* blockExtra, int N, int g, int finish, int split,
-                 int refill, unsigned long long m, unsigned long long M, hipStream_t s);
+                 int refill, unsigned long long m, unsigned long long M, hipStream_t s,
+                 int stack = 0, int stack_cap = -1);
 void launch_pfsp_x(DevCtl* ctl, const PFSPNode* pool, PFSPNode* childbuf, uint32_t* bc,
                    unsigned long long* bs, int jobs, int machines, int lbk,
                    const PfspDevTables& tb, unsigned long long m, unsigned long long M,

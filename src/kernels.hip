@@ -681,11 +681,18 @@ __device__ inline unsigned long long derive_chunk(const DevCtl* ctl, unsigned lo
 // not all fit), and a wave that has `refill` idle lanes (or only idle lanes)
 // hands all of them the next unclaimed entries from an LDS counter
 // (nq_refill_now): which lane walks what varies, the sums do not.
+// SPLIT == NQ_X_STACK: the wave-stack finisher (nq_finish.hpp). A lane owns a
+// row and never backtracks; children with an inner row below them go onto the
+// wave's own LDS stack of NQ_STACK_CAP entries, idle lanes take them off it or
+// draw whole jobs from jobq through one LDS counter. No split pass, no sub-job
+// queue, no block barrier inside phase C. stack_cap (<= NQ_STACK_CAP) is the
+// height past which children are walked instead of pushed (a test knob).
+constexpr int NQ_X_STACK = 3;
 template <bool G1, int SPLIT>
 __global__ void k_nq_x(const DevCtl* ctl, const NQNode* pool, NQNode* childbuf,
                        uint32_t* blockCounts, unsigned long long* blockSols,
                        unsigned long long* blockExtra, int N, int g, int finish, int refill,
-                       unsigned long long m, unsigned long long M) {
+                       int stack_cap, unsigned long long m, unsigned long long M) {
   __shared__ NQNode s[EMIT_TILE / 4 + 2];  // N >= 4 (engine falls back below)
   __shared__ uint64_t pmask[EMIT_TILE / 4 + 2];  // per-parent cols/d1/d2 (nq_pmask_pack)
   __shared__ uint16_t jobq[EMIT_TILE];  // finisher jobs: nq_job_ref(local parent id, column)
@@ -805,6 +812,69 @@ __global__ void k_nq_x(const DevCtl* ctl, const NQNode* pool, NQNode* childbuf,
             return true;
           },
           msk, g);
+    } else if constexpr (SPLIT == NQ_X_STACK) {
+      __shared__ uint64_t stk[BLOCK / 64][NQ_STACK_CAP];
+      __shared__ uint32_t jhead;
+      static_assert(sizeof(s) + sizeof(pmask) + sizeof(jobq) + sizeof(jobcnt) + sizeof(stk) +
+                            sizeof(jhead) + 4 * sizeof(uint32_t) +
+                            4 * sizeof(unsigned long long) + 16 <=
+                        20480,
+                    "k_nq_x's LDS (with the scan / reduce scratch and padding) must leave "
+                    "eight blocks per CU");
+      if (threadIdx.x == 0) jhead = 0;
+      __syncthreads();
+      uint64_t* const my = stk[wid];  // this wave's stack; no other wave touches it
+      const unsigned long long lt = (1ull << lane) - 1ull;
+      const uint32_t T = static_cast<uint32_t>(refill);
+      const uint32_t cap = static_cast<uint32_t>(stack_cap);  // <= NQ_STACK_CAP (launch_nq_x)
+      NqRow r = {0, 0, 0, 0, 0, 0, 0};
+      uint32_t sp = 0;   // wave-uniform: ballots and the broadcast counter alone move it
+      bool more = true;  // wave-uniform
+      unsigned long long im = ~0ull;  // every lane starts idle, so the wave starts by acting
+      uint32_t nidle = 64u;
+      // Why it ends: see nq_stack_act (nq_finish.hpp). The iterations that only
+      // step and push are an inner loop of their own; the fetch is behind the
+      // scalar branch nq_stack_act.
+      for (;;) {
+        if (nq_stack_done(nidle, 64u, sp, more)) break;
+        const bool idle = r.cand == 0;
+        const uint32_t rank = static_cast<uint32_t>(__popcll(im & lt));
+        const uint32_t take = nq_stack_take(nidle, sp);
+        // rank < take <= sp: my[sp - 1 - rank] is inside [0, sp)
+        if (idle && rank < take) nq_row_load_entry(r, my[sp - 1u - rank], msk);
+        sp -= take;
+        if (more && nidle > take) {
+          const uint32_t rem = nq_stack_draw(nidle - take, njobs, BLOCK / 64);
+          uint32_t got = 0;
+          if (lane == 0) got = atomicAdd(&jhead, rem);
+          got = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(got)));
+          more = !nq_refill_drains(got, rem, njobs);
+          const uint32_t qi = got + rank - take;
+          // qi < njobs <= EMIT_TILE: inside jobq
+          if (idle && rank >= take && rank - take < rem && qi < njobs) {
+            uint32_t jc, jd1, jd2;
+            const int row = job_state(jobq[qi], jc, jd1, jd2);
+            nq_row_load_job<G1>(r, jc, jd1, jd2, row, N, msk, g);
+          }
+        }
+        do {
+          uint32_t nc, n1, n2;
+          const bool push = nq_row_step<G1>(r, msk, g, nc, n1, n2);  // idle lanes pass through
+          if (nq_stack_can_push(sp, 64u, cap)) {  // scalar: sp + 64 <= cap <= NQ_STACK_CAP
+            const unsigned long long pm = __builtin_amdgcn_ballot_w64(push);
+            if (push)
+              my[sp + static_cast<uint32_t>(__popcll(pm & lt))] =
+                  nq_entry_pack(nc, n1, n2, r.h - 1u);
+            sp += static_cast<uint32_t>(__popcll(pm));
+          } else if (push) {
+            nq_row_walk<G1>(r, nc, n1, n2, N, msk, g);
+          }
+          im = __builtin_amdgcn_ballot_w64(r.cand == 0);
+          nidle = static_cast<uint32_t>(__popcll(im));
+        } while (!nq_stack_act(nidle, 64u, T, sp, more));
+      }
+      st.tree = r.tree;
+      st.sol = r.sol;
     } else {
       // phase C1, split: thread t counts the sub-jobs of jobs t, t + 256, ...
       // (and the nodes of the rows it enumerates); a block scan per row of 256
@@ -1859,13 +1929,19 @@ int devpool_stride(int lbk) {
 void launch_nq_x(const DevCtl* ctl, const NQNode* pool, NQNode* childbuf,
                  uint32_t* blockCounts, unsigned long long* blockSols,
                  unsigned long long* blockExtra, int N, int g, int finish, int split,
-                 int refill, unsigned long long m, unsigned long long M, hipStream_t s) {
+                 int refill, unsigned long long m, unsigned long long M, hipStream_t s,
+                 int stack, int stack_cap) {
   refill = refill < 1 ? 1 : refill > 64 ? 64 : refill;  // idle lanes of a 64-lane wave
+  // the kernel's stack writes stay below stack_cap, which stays inside the array
+  stack_cap = stack_cap < 0 || stack_cap > NQ_STACK_CAP ? NQ_STACK_CAP : stack_cap;
   auto go = [&](auto kernel) {
     hipLaunchKernelGGL(kernel, dim3(devpool_grid(M, N, 1)), dim3(BLOCK), 0, s, ctl, pool,
-                       childbuf, blockCounts, blockSols, blockExtra, N, g, finish, refill, m, M);
+                       childbuf, blockCounts, blockSols, blockExtra, N, g, finish, refill,
+                       stack_cap, m, M);
   };
-  if (g == 1)
+  if (stack)
+    g == 1 ? go(k_nq_x<true, NQ_X_STACK>) : go(k_nq_x<false, NQ_X_STACK>);
+  else if (g == 1)
     split <= 0 ? go(k_nq_x<true, 0>) : split == 1 ? go(k_nq_x<true, 1>) : go(k_nq_x<true, 2>);
   else
     split <= 0 ? go(k_nq_x<false, 0>) : split == 1 ? go(k_nq_x<false, 1>)

@@ -328,6 +328,172 @@ NQ_HD inline bool nq_refill_drains(uint32_t got, uint32_t nidle, uint32_t nsub) 
 }
 inline constexpr int NQ_REFILL_DEFAULT = 24;  // GATS_NQ_REFILL's default
 
+// ---------------------------------------------------------------------------
+// Wave-stack finisher (k_nq_x's stack variant and nq_finish_stack_cpu).
+//
+// A lane owns one ROW, not a walk: it takes that row's candidates one per
+// iteration and never backtracks. A child that has children of its own in an
+// inner row is pushed, as one 64-bit entry, onto a node stack that the lane's
+// wave owns; a lane whose row is exhausted takes any entry off that stack, or
+// a job off the block's job queue. So there is no pop path, no split pass and
+// no sub-job queue, and inside a wave no lane waits on another lane's walk
+// while the stack holds work.
+//
+// Stack entry: cols | d1 << 20 | d2 << 40 | h << 60 (nq_pmask_pack plus four
+// bits). The masks are in nq_step_down's form: seen from the node's first
+// empty row, below 2^N, N <= 20. h is the number of rows below that row; a
+// pushed node has 1 <= h <= NQ_FLAT_LEVELS_DEV - 2.
+// ---------------------------------------------------------------------------
+inline constexpr int NQ_STACK_H_BITS = 4;
+inline constexpr int NQ_STACK_H_SHIFT = 3 * NQ_PMASK_BITS;
+static_assert(NQ_STACK_H_SHIFT + NQ_STACK_H_BITS <= 64, "a stack entry is one 64-bit word");
+static_assert(NQ_FLAT_LEVELS_DEV - 1 < (1 << NQ_STACK_H_BITS), "h of a job's root fits the field");
+NQ_HD inline uint64_t nq_entry_pack(uint32_t cols, uint32_t d1, uint32_t d2, uint32_t h) {
+  return nq_pmask_pack(cols, d1, d2) | static_cast<uint64_t>(h) << NQ_STACK_H_SHIFT;
+}
+NQ_HD inline uint32_t nq_entry_unpack(uint64_t w, uint32_t& cols, uint32_t& d1, uint32_t& d2) {
+  nq_pmask_unpack(w, cols, d1, d2);
+  return static_cast<uint32_t>(w >> NQ_STACK_H_SHIFT) & ((1u << NQ_STACK_H_BITS) - 1u);
+}
+
+// Per-wave stack capacity [entries] of the kernel: four stacks of 312 entries
+// are 9,984 B, which with the 10,424 B of the shared phases and the job
+// counter keeps k_nq_x within 20,480 B of LDS, eight blocks per CU (a
+// static_assert in the kernel). The largest peak scripts/nq_lane_model.py
+// sees is recorded in docs/DESIGN.md; past the capacity the fallback below is
+// exact, only slower. -DGATS_NQ_STACK_CAP=n builds another size.
+#ifndef GATS_NQ_STACK_CAP
+#define GATS_NQ_STACK_CAP 312
+#endif
+inline constexpr int NQ_STACK_CAP = GATS_NQ_STACK_CAP;
+inline constexpr int NQ_STACK_DEFAULT = 1;  // GATS_NQ_STACK's default
+
+// Lane state: a row (masks seen from it, rows below it) and its candidates
+// that are still to be taken. cand == 0: the lane is idle.
+struct NqRow {
+  uint32_t cols, d1, d2, cand;
+  uint32_t h;
+  uint32_t tree, sol;  // 32 bits hold a block's whole queue (see k_nq_x)
+};
+
+// A job off the queue: its root's free mask is evaluated here for the first
+// time (g times when G1 == false). A root in the bottom row is counted at once.
+template <bool G1>
+NQ_HD inline void nq_row_load_job(NqRow& r, uint32_t c, uint32_t d1, uint32_t d2, int row, int N,
+                                  uint32_t msk, int g) {
+  r.cols = c;
+  r.d1 = d1;
+  r.d2 = d2;
+  r.h = static_cast<uint32_t>(N - 1 - row);
+  const uint32_t occ = c | d1 | d2;
+  r.cand = G1 ? (~occ & msk) : nq_free_occ_g(occ, msk, g);
+  if (r.h == 0) {
+    const uint32_t n = static_cast<uint32_t>(__builtin_popcount(r.cand));
+    r.tree += n;
+    r.sol += n;
+    r.cand = 0;
+  }
+}
+
+// An entry off the stack: its free mask was evaluated when it was pushed, so
+// it is re-derived plainly. It is not empty (only such nodes are pushed).
+NQ_HD inline void nq_row_load_entry(NqRow& r, uint64_t e, uint32_t msk) {
+  r.h = nq_entry_unpack(e, r.cols, r.d1, r.d2);
+  r.cand = ~(r.cols | r.d1 | r.d2) & msk;
+}
+
+// Row step (h >= 1 where cand != 0): take the lowest candidate and count it;
+// count its children with a popcount when they are the bottom row. Returns
+// true when the child (nc, n1, n2), whose row has h - 1 rows below it, has
+// children in an inner row: the caller pushes it, or walks it (nq_row_walk).
+// An idle lane (cand == 0) passes through unchanged and returns false, so a
+// wave needs no branch around the step.
+template <bool G1>
+NQ_HD inline bool nq_row_step(NqRow& r, uint32_t msk, int g, uint32_t& nc, uint32_t& n1,
+                              uint32_t& n2) {
+  const bool active = r.cand != 0;
+  const uint32_t bit = r.cand & (0u - r.cand);
+  r.cand ^= bit;
+  r.tree += active;
+  nc = r.cols;
+  n1 = r.d1;
+  n2 = r.d2;
+  nq_step_down(nc, n1, n2, bit, msk);
+  const uint32_t occ = nc | n1 | n2;
+  uint32_t nf = G1 ? (~occ & msk) : nq_free_occ_g(occ, msk, g);
+  nf = active ? nf : 0u;
+  const uint32_t n = r.h == 1 ? static_cast<uint32_t>(__builtin_popcount(nf)) : 0u;
+  r.tree += n;
+  r.sol += n;
+  return r.h != 1 && nf != 0;
+}
+
+// Overflow fallback: the lane walks the child nq_row_step returned to the end
+// with the flat walk (load, then pop / take), then returns to its row. The
+// child was counted and its free mask evaluated by the row step, so the load
+// is plain; the walk counts every node below it, as pushing it would.
+template <bool G1>
+NQ_HD inline void nq_row_walk(NqRow& r, uint32_t nc, uint32_t n1, uint32_t n2, int N, uint32_t msk,
+                              int g) {
+  NqFlat<NQ_FLAT_LEVELS_DEV> w;
+  w.tree = 0;
+  w.sol = 0;
+  w.template load<true>(nc, n1, n2, N - static_cast<int>(r.h), N, msk, 1);
+  while (w.cand != 0 || w.stack > 1) {
+    if (w.cand == 0) w.pop(msk);
+    if (w.cand) w.template take<G1>(msk, g);
+  }
+  r.tree += w.tree;
+  r.sol += w.sol;
+}
+
+// Wave rule. Wave-uniform state: sp, the stack's height; more, whether the
+// block's job queue may still hold a job for this wave (cleared by the draw
+// that reaches the queue's end). Every iteration the wave counts its idle
+// lanes. It stops stepping and acts (nq_stack_act) when all of its `lanes`
+// lanes are idle, or when at least T are and there is work for them (sp != 0
+// or more). Acting it either leaves (nq_stack_done: all idle, stack empty,
+// queue exhausted) or refills: the idle lanes take min(nidle, sp) entries off
+// the top of the stack (nq_stack_take), and if idle lanes remain and `more`
+// holds they draw job indices from the block's counter (nq_stack_draw: one per
+// idle lane up to the wave's even share of the queue), as the split finisher's
+// lanes draw sub-jobs (nq_refill_drains sets more = false).
+// Pushes happen only while sp + lanes <= cap (nq_stack_can_push, checked once
+// per iteration, before that iteration's at most `lanes` pushes, so sp <= cap
+// always); otherwise the lane walks the child (nq_row_walk).
+//
+// The loop ends: (1) an iteration in which a lane is active takes one
+// candidate off that lane's row, and every candidate is a tree node that is
+// taken once, by one lane, from a row loaded once (a job is drawn by one lane,
+// an entry is popped once), or inside a fallback walk, which is finite; so the
+// iterations with an active lane number at most the nodes below the jobs.
+// (2) An iteration with no active lane satisfies nq_stack_act, so it is the
+// last one before the wave acts, and the wave steps at least once after each
+// refill: iterations <= nodes + refills. (3) A refill takes at least one entry
+// off the stack (sp != 0) or advances the job counter by at least one
+// (sp == 0, so `more` holds, else the wave would have left); the entries taken
+// are bounded by the pushes, i.e. by the nodes, and a wave draws past the
+// queue's end at most once, so a block's refills are at most nodes + jobs +
+// waves. Waves share only the job counter, so none waits for another.
+NQ_HD inline bool nq_stack_act(uint32_t nidle, uint32_t lanes, uint32_t T, uint32_t sp, bool more) {
+  return nidle >= lanes || ((sp != 0 || more) && nidle >= T);
+}
+NQ_HD inline bool nq_stack_done(uint32_t nidle, uint32_t lanes, uint32_t sp, bool more) {
+  return nidle >= lanes && sp == 0 && !more;
+}
+NQ_HD inline uint32_t nq_stack_take(uint32_t nidle, uint32_t sp) { return nidle < sp ? nidle : sp; }
+// Jobs one refill draws for `rem` idle lanes: at most the wave's even share of
+// the block's queue, at least one. So the block's waves start with about the
+// same number of jobs each (a wave cannot take work off another wave's stack),
+// instead of the first waves to arrive taking `lanes` jobs each.
+NQ_HD inline uint32_t nq_stack_draw(uint32_t rem, uint32_t njobs, uint32_t waves) {
+  const uint32_t share = (njobs + waves - 1u) / waves;
+  return rem < share ? rem : share != 0 ? share : 1u;
+}
+NQ_HD inline bool nq_stack_can_push(uint32_t sp, uint32_t lanes, uint32_t cap) {
+  return sp + lanes <= cap;
+}
+
 // Rounds cut. off[0..njobs] are the jobs' exclusive sub-job offsets in queue
 // order (off[njobs] = all of them). A round takes the longest run of jobs
 // [jb, je) whose sub-jobs fit `qcap` entries; returns je (== jb only when job
