@@ -12,7 +12,7 @@
 #include "gpu_api.hpp"
 #include "nodes.hpp"
 #include "nq_finish.hpp"
-#include "nq_finish_stack_cpu.hpp"
+#include "nq_finish_cpu.hpp"
 #include "pool.hpp"
 #include "search_host.hpp"
 #include "share_selftest.hpp"
@@ -75,16 +75,8 @@ py::tuple nq_finish_count(uint32_t cols, uint32_t d1, uint32_t d2, int row, int 
   st.tree = 0;
   st.sol = 0;
   const uint32_t msk = (1u << N) - 1u;
-  bool handed = false;
-  nq_flat_run<LEVELS, true>(
-      st,
-      [&](NqFlat<LEVELS>& w) {
-        if (handed) return false;
-        handed = true;
-        w.template load<true>(cols, d1, d2, row, N, msk, 1);
-        return true;
-      },
-      msk, 1);
+  st.template load<true>(cols, d1, d2, row, N, msk, 1);
+  st.template exhaust<true>(msk, 1);
   return py::make_tuple(static_cast<uint64_t>(st.tree), static_cast<uint64_t>(st.sol));
 }
 
@@ -98,206 +90,26 @@ py::tuple nq_finish_count_cpu(uint32_t cols, uint32_t d1, uint32_t d2, int row, 
                                     : nq_finish_count<NQ_FLAT_LEVELS_MAX>(cols, d1, d2, row, N);
 }
 
-// CPU run of k_nq_x's split finisher over one block's job queue, with the
-// kernel's own functions in sequence: count and rank the sub-jobs, cut the
-// queue into rounds of at most `qcap` entries, write each round's entries and
-// drain them with one flat loop. jobs: (cols, d1, d2, row) states as
-// nq_finish_count_cpu takes them. Returns (tree, sol, entries, rounds).
-template <bool G1>
-py::tuple nq_finish_block(const std::vector<std::array<uint32_t, 4>>& jobs, int N, int g,
-                          int split, uint32_t qcap) {
-  const uint32_t msk = (1u << N) - 1u;
-  const uint32_t njobs = static_cast<uint32_t>(jobs.size());
-  auto levels = [&](uint32_t q) {
-    return nq_split_levels(split, N - static_cast<int>(jobs[q][3]));
-  };
-  std::vector<uint32_t> off(njobs + 1, 0);
-  uint32_t nodes = 0;
-  for (uint32_t q = 0; q < njobs; q++) {
-    const uint32_t n = nq_split_job<G1, false>(jobs[q][0], jobs[q][1], jobs[q][2], levels(q), msk,
-                                               g, nodes, [](uint32_t, uint32_t, uint32_t) {});
-    if (n > qcap)
-      throw std::invalid_argument("qcap " + std::to_string(qcap) + " is below the " +
-                                  std::to_string(n) + " sub-jobs of job " + std::to_string(q));
-    off[q + 1] = off[q] + n;
-  }
-  NqFlat<NQ_FLAT_LEVELS_DEV> st;
-  st.tree = 0;
-  st.sol = 0;
-  std::vector<uint32_t> subq(qcap);
-  uint32_t rounds = 0;
-  for (uint32_t jb = 0; jb < njobs; rounds++) {
-    const uint32_t je = nq_round_end(off.data(), jb, njobs, qcap);
-    const uint32_t nsub = off[je] - off[jb];
-    for (uint32_t q = jb; q < je; q++) {
-      uint32_t w = off[q] - off[jb], unused = 0;
-      nq_split_job<true, true>(jobs[q][0], jobs[q][1], jobs[q][2], levels(q), msk, 1, unused,
-                               [&](uint32_t nc, uint32_t c1, uint32_t c2) {
-                                 subq[w++] = nq_sub_encode(q, nc, c1, c2);
-                               });
-    }
-    uint32_t head = 0;
-    nq_flat_run<NQ_FLAT_LEVELS_DEV, G1>(
-        st,
-        [&](NqFlat<NQ_FLAT_LEVELS_DEV>& w) {
-          if (head >= nsub) return false;
-          const uint32_t e = subq[head++];
-          const auto& j = jobs[nq_sub_ref(e)];
-          nq_sub_load<G1>(w, e, j[0], j[1], j[2], static_cast<int>(j[3]), N, msk, g);
-          return true;
-        },
-        msk, g);
-    jb = je;
-  }
-  return py::make_tuple(static_cast<uint64_t>(nodes) + st.tree, static_cast<uint64_t>(st.sol),
-                        off[njobs], rounds);
+// The CPU twins of k_nq_x's drains over one block's job queue (nq_finish_cpu.hpp).
+// jobs: (cols, d1, d2, row) states as nq_finish_count_cpu takes them.
+// Split finisher, one flat loop: (tree, sol, entries, rounds).
+py::tuple nq_finish_block_cpu(const NqJobs& jobs, int N, int g, int split, long long qcap) {
+  const NqSplitRun r = nq_finish_block(jobs, N, g, split, qcap);
+  return py::make_tuple(r.tree, r.sol, r.entries, r.rounds);
 }
 
-py::tuple nq_finish_block_cpu(const std::vector<std::array<uint32_t, 4>>& jobs, int N, int g,
-                              int split, long long qcap) {
-  if (N < 1 || N > MAX_JOBS) throw std::invalid_argument("N must be in 1..20");
-  if (g < 1) throw std::invalid_argument("g must be >= 1");
-  if (split < 0 || split > NQ_SPLIT_MAX) throw std::invalid_argument("split must be in 0..2");
-  if (qcap < 1 || qcap > (1 << 20)) throw std::invalid_argument("qcap must be in 1..2^20");
-  if (jobs.size() > 1024) throw std::invalid_argument("a block holds at most 1024 jobs");
-  for (const auto& j : jobs) {
-    const int rows = N - static_cast<int>(j[3]);
-    if (rows < 1 || rows > NQ_FLAT_LEVELS_DEV)
-      throw std::invalid_argument("every job needs 1..8 empty rows");
-    if ((j[0] | j[1] | j[2]) >> N) throw std::invalid_argument("mask bits at or above column N");
-  }
-  return g == 1 ? nq_finish_block<true>(jobs, N, g, split, static_cast<uint32_t>(qcap))
-                : nq_finish_block<false>(jobs, N, g, split, static_cast<uint32_t>(qcap));
+// Split finisher as `waves` x `lanes` walks in lockstep:
+// (tree, sol, entries, rounds, refills, steps).
+py::tuple nq_finish_wave_cpu(const NqJobs& jobs, int N, int g, int split, long long qcap,
+                             int refill, int lanes, int waves) {
+  const NqSplitRun r = nq_finish_wave(jobs, N, g, split, qcap, refill, lanes, waves);
+  return py::make_tuple(r.tree, r.sol, r.entries, r.rounds, r.refills, r.steps);
 }
 
-// CPU run of k_nq_x's drain as its waves run it: `waves` x `lanes` flat walks
-// stepped in lockstep, every wave deciding with the kernel's own rule
-// (nq_refill_now / nq_refill_drains / nq_wave_done) when its idle lanes fetch,
-// the waves taking turns, one loop iteration each, on one queue head. The
-// split pass, the rounds and the entries are nq_finish_block's. Returns
-// (tree, sol, entries, rounds, refills, steps); steps counts the waves' loop
-// iterations. Every iteration but a wave's last either steps an active lane
-// or is a refill, and the lane steps of a round sum to the walk lengths of
-// its sub-jobs whichever lane walks them, so steps <= walk lengths + refills:
-// the loop throws when it passes that bound instead of spinning.
-template <bool G1>
-py::tuple nq_finish_wave(const std::vector<std::array<uint32_t, 4>>& jobs, int N, int g, int split,
-                         uint32_t qcap, uint32_t T, uint32_t lanes, uint32_t waves) {
-  using Flat = NqFlat<NQ_FLAT_LEVELS_DEV>;
-  const uint32_t msk = (1u << N) - 1u;
-  const uint32_t njobs = static_cast<uint32_t>(jobs.size());
-  auto levels = [&](uint32_t q) {
-    return nq_split_levels(split, N - static_cast<int>(jobs[q][3]));
-  };
-  std::vector<uint32_t> off(njobs + 1, 0);
-  uint32_t nodes = 0;
-  for (uint32_t q = 0; q < njobs; q++) {
-    const uint32_t n = nq_split_job<G1, false>(jobs[q][0], jobs[q][1], jobs[q][2], levels(q), msk,
-                                               g, nodes, [](uint32_t, uint32_t, uint32_t) {});
-    if (n > qcap)
-      throw std::invalid_argument("qcap " + std::to_string(qcap) + " is below the " +
-                                  std::to_string(n) + " sub-jobs of job " + std::to_string(q));
-    off[q + 1] = off[q] + n;
-  }
-  auto load = [&](Flat& w, uint32_t e) {
-    const auto& j = jobs[nq_sub_ref(e)];
-    nq_sub_load<G1>(w, e, j[0], j[1], j[2], static_cast<int>(j[3]), N, msk, g);
-  };
-  auto step = [&](Flat& w) {  // the kernel's loop body below the fetch
-    if (w.cand == 0 && w.stack > 1) w.pop(msk);
-    if (w.cand) w.template take<G1>(msk, g);
-  };
-  std::vector<Flat> st(static_cast<size_t>(waves) * lanes);
-  for (auto& w : st) w.tree = w.sol = 0;
-  std::vector<uint32_t> subq(qcap);
-  uint64_t refills = 0, steps = 0;
-  uint32_t rounds = 0;
-  for (uint32_t jb = 0; jb < njobs; rounds++) {
-    const uint32_t je = nq_round_end(off.data(), jb, njobs, qcap);
-    const uint32_t nsub = off[je] - off[jb];
-    for (uint32_t q = jb; q < je; q++) {
-      uint32_t w = off[q] - off[jb], unused = 0;
-      nq_split_job<true, true>(jobs[q][0], jobs[q][1], jobs[q][2], levels(q), msk, 1, unused,
-                               [&](uint32_t nc, uint32_t c1, uint32_t c2) {
-                                 subq[w++] = nq_sub_encode(q, nc, c1, c2);
-                               });
-    }
-    uint64_t walk = 0;  // the round's bound: one lane walks every entry
-    for (uint32_t i = 0; i < nsub; i++) {
-      Flat w;
-      w.tree = w.sol = 0;
-      for (load(w, subq[i]); !nq_lane_idle(w.cand, w.stack); walk++) step(w);
-    }
-    const uint64_t steps0 = steps, refills0 = refills;
-    uint32_t head = 0, running = waves;
-    std::vector<char> drained(waves, 0), done(waves, 0);
-    for (auto& w : st) w.cand = 0, w.stack = 0;
-    while (running) {
-      for (uint32_t v = 0; v < waves; v++) {
-        if (done[v]) continue;
-        Flat* wl = &st[static_cast<size_t>(v) * lanes];
-        uint32_t nidle = 0;
-        for (uint32_t l = 0; l < lanes; l++) nidle += nq_lane_idle(wl[l].cand, wl[l].stack);
-        if (nq_refill_now(nidle, lanes, T, drained[v] != 0)) {
-          const uint32_t got = head;
-          head += nidle;
-          refills++;
-          drained[v] = nq_refill_drains(got, nidle, nsub);
-          uint32_t qi = got;
-          for (uint32_t l = 0; l < lanes; l++)
-            if (nq_lane_idle(wl[l].cand, wl[l].stack)) {
-              if (qi < nsub) load(wl[l], subq[qi]);
-              qi++;
-            }
-        } else if (nq_wave_done(nidle, lanes, drained[v] != 0)) {
-          done[v] = 1;
-          running--;
-          continue;
-        }
-        for (uint32_t l = 0; l < lanes; l++) step(wl[l]);
-        steps++;
-        if (steps - steps0 > walk + (refills - refills0))
-          throw std::runtime_error("the drain passed its bound of " + std::to_string(walk) +
-                                   " lane steps + " + std::to_string(refills - refills0) +
-                                   " refills in round " + std::to_string(rounds));
-      }
-    }
-    jb = je;
-  }
-  uint64_t tree = nodes, sol = 0;
-  for (const auto& w : st) tree += w.tree, sol += w.sol;
-  return py::make_tuple(tree, sol, off[njobs], rounds, refills, steps);
-}
-
-py::tuple nq_finish_wave_cpu(const std::vector<std::array<uint32_t, 4>>& jobs, int N, int g,
-                             int split, long long qcap, int refill, int lanes, int waves) {
-  if (N < 1 || N > MAX_JOBS) throw std::invalid_argument("N must be in 1..20");
-  if (g < 1) throw std::invalid_argument("g must be >= 1");
-  if (split < 1 || split > NQ_SPLIT_MAX) throw std::invalid_argument("split must be in 1..2");
-  if (qcap < 1 || qcap > (1 << 20)) throw std::invalid_argument("qcap must be in 1..2^20");
-  if (lanes < 1 || lanes > 64) throw std::invalid_argument("lanes must be in 1..64");
-  if (waves < 1 || waves > 16) throw std::invalid_argument("waves must be in 1..16");
-  // a threshold above the wave's width is rejected, not clamped: it could only
-  // ever act as the all-idle rule, which `refill == lanes` already names
-  if (refill < 1 || refill > lanes) throw std::invalid_argument("refill must be in 1..lanes");
-  if (jobs.size() > 1024) throw std::invalid_argument("a block holds at most 1024 jobs");
-  for (const auto& j : jobs) {
-    const int rows = N - static_cast<int>(j[3]);
-    if (rows < 1 || rows > NQ_FLAT_LEVELS_DEV)
-      throw std::invalid_argument("every job needs 1..8 empty rows");
-    if ((j[0] | j[1] | j[2]) >> N) throw std::invalid_argument("mask bits at or above column N");
-  }
-  const auto q = static_cast<uint32_t>(qcap);
-  const auto T = static_cast<uint32_t>(refill);
-  const auto L = static_cast<uint32_t>(lanes), W = static_cast<uint32_t>(waves);
-  return g == 1 ? nq_finish_wave<true>(jobs, N, g, split, q, T, L, W)
-                : nq_finish_wave<false>(jobs, N, g, split, q, T, L, W);
-}
-
-// CPU run of k_nq_x's wave-stack finisher for one block (nq_finish_stack_cpu.hpp).
-// Returns (tree, sol, iterations per wave, peak sp per wave, fallback walks).
-py::tuple nq_finish_stack_cpu(const std::vector<std::array<uint32_t, 4>>& jobs, int N, int g,
-                              int refill, int waves, int lanes, long long cap) {
+// Wave-stack finisher:
+// (tree, sol, iterations per wave, peak sp per wave, fallback walks).
+py::tuple nq_finish_stack_cpu(const NqJobs& jobs, int N, int g, int refill, int waves, int lanes,
+                              long long cap) {
   const NqStackRun r = nq_finish_stack(jobs, N, g, refill, waves, lanes, cap);
   return py::make_tuple(r.tree, r.sol, r.iters, r.peak_sp, r.fallbacks);
 }
@@ -574,8 +386,8 @@ py::tuple nq_devpool_step_py(const py::bytes& nodes, int N, int g, int finish, l
   DevpoolStepCtl c;
   {
     py::gil_scoped_release rel;
-    c = nq_devpool_step(v, N, g, finish, static_cast<unsigned long long>(m), Mv, cap, presum,
-                        device, split, refill, stack, stack_cap);
+    c = nq_devpool_step(v, N, g, {finish, split, refill, stack, stack_cap},
+                        static_cast<unsigned long long>(m), Mv, cap, presum, device);
   }
   return py::make_tuple(nodes_to_bytes(v.data(), v.size()), step_ctl_to_dict(c));
 }
@@ -629,8 +441,8 @@ py::list nq_devpool_chain_py(const py::bytes& nodes, int N, const std::vector<lo
   std::vector<DevpoolSnapshot<NQNode>> snaps;
   {
     py::gil_scoped_release rel;
-    snaps = nq_devpool_chain(v, N, g, finish, static_cast<unsigned long long>(m), w, cap,
-                             presum, device, split, refill, stack, stack_cap);
+    snaps = nq_devpool_chain(v, N, g, {finish, split, refill, stack, stack_cap},
+                             static_cast<unsigned long long>(m), w, cap, presum, device);
   }
   return chain_to_list(snaps);
 }

@@ -516,12 +516,37 @@ int nq_stack_default() {
   return stack;
 }
 
+NqFinishOpts nq_finish_opts(int g, const NqFinishOpts& asked) {
+  if (asked.split > NQ_SPLIT_MAX) throw std::invalid_argument("split must be in 0..2, or < 0");
+  if (asked.refill == 0 || asked.refill > 64)
+    throw std::invalid_argument("refill must be in 1..64, or < 0");
+  // stack = 1 is the finisher of the default split only; stack_cap is its knob
+  if (asked.stack > 1) throw std::invalid_argument("stack must be 0 or 1, or < 0");
+  if (asked.stack == 1 && asked.split >= 0)
+    throw std::invalid_argument("stack = 1 takes no explicit split");
+  if (asked.stack_cap > NQ_STACK_CAP)
+    throw std::invalid_argument("stack_cap must be in 0.." + std::to_string(NQ_STACK_CAP) +
+                                ", or < 0");
+  NqFinishOpts o = asked;
+  if (o.split < 0) o.split = nq_split_default();
+  if (o.refill < 0) o.refill = nq_refill_default();
+  o.stack = asked.stack < 0 ? (asked.split < 0 && g == 1 && nq_stack_default() == 1)
+                            : asked.stack != 0;
+  if (o.stack_cap < 0) o.stack_cap = NQ_STACK_CAP;
+  return o;
+}
+
+// The engines' finisher: GATS_NQ_FINISH levels, every other knob its default.
+static NqFinishOpts nq_engine_finisher(int g) {
+  return nq_finish_opts(g, {nq_finish_depth()});
+}
+
 DevpoolMultiOut nq_devpool_multi(Pool<NQNode>& pool, int N, int g, int m, int M,
                                  const std::vector<int>& devices,
                                  unsigned long long capacity, Result& r) {
   if (static_cast<unsigned long long>(M) * N > (1ull << 31))
     throw std::invalid_argument("devpool requires M * N <= 2^31");
-  return devpool_multi(NqDevProblem(N, g, nq_finish_depth()), pool, devpool_slices(),
+  return devpool_multi(NqDevProblem(N, g, nq_engine_finisher(g)), pool, devpool_slices(),
                        /*deep_levels=*/10, /*best0=*/0, m, M, devices, capacity, nullptr, r,
                        {});
 }
@@ -928,7 +953,7 @@ static std::vector<typename Problem::Node> gpu_frontier(const Problem& problem,
 std::vector<NQNode> nq_gpu_frontier(int N, int g, size_t target, int device,
                                     uint64_t& tree, uint64_t& sol) {
   DevCtl fin;
-  std::vector<NQNode> nodes = gpu_frontier(NqDevProblem(N, g, nq_finish_depth()), nq_root(),
+  std::vector<NQNode> nodes = gpu_frontier(NqDevProblem(N, g, nq_engine_finisher(g)), nq_root(),
                                            target, device, /*best0=*/0, fin);
   tree = fin.tree;
   sol = fin.sol;

@@ -9,6 +9,7 @@
 #include <thread>
 #include <vector>
 
+#include "gpu_api.hpp"
 #include "nodes.hpp"
 #include "search_host.hpp"
 
@@ -205,21 +206,28 @@ void validate_pfsp_step(const std::vector<PFSPNode>& nodes, int inst, const std:
                         unsigned long long m, unsigned long long M,
                         unsigned long long capacity, int geom, const std::string& presum,
                         const std::string& br = "fwd");
+// The finisher knobs as a caller gives them (an NqFinishOpts that
+// nq_finish_opts has not resolved yet; finish passes through):
 // split: levels the finisher jobs are split (0..2), < 0 = the engine's default
 // refill: idle lanes at which a wave of the split finisher refills (1..64),
 // < 0 = the engine's default
 // stack: 1 = the wave-stack finisher, 0 = the split one, < 0 = the engine's
-// rule: the stack finisher where split < 0 too, g == 1 and nq_stack_default() is 1
+// rule: the stack finisher where split < 0 too, g == 1 and nq_stack_default() is 1;
+// an explicit split keeps the split kernels, and so does g > 1 (the g repeats
+// are issued per wave iteration, of which the stack schedule has far fewer:
+// BASELINE.md "Wave-stack finisher")
 // stack_cap: the stack height per wave past which children are walked instead
 // of pushed (0..NQ_STACK_CAP), < 0 = NQ_STACK_CAP
+// The defaults are GATS_NQ_SPLIT / GATS_NQ_REFILL / GATS_NQ_STACK, read once.
+// nq_finish_opts throws std::invalid_argument for a value outside these ranges.
 int nq_split_default();
 int nq_refill_default();
 int nq_stack_default();
-DevpoolStepCtl nq_devpool_step(std::vector<NQNode>& nodes, int N, int g, int finish,
-                               unsigned long long m, unsigned long long M,
-                               unsigned long long capacity, const std::string& presum,
-                               int device, int split = -1, int refill = -1, int stack = -1,
-                               int stack_cap = -1);
+NqFinishOpts nq_finish_opts(int g, const NqFinishOpts& asked);
+DevpoolStepCtl nq_devpool_step(std::vector<NQNode>& nodes, int N, int g,
+                               const NqFinishOpts& finisher, unsigned long long m,
+                               unsigned long long M, unsigned long long capacity,
+                               const std::string& presum, int device);
 DevpoolStepCtl pfsp_devpool_step(std::vector<PFSPNode>& nodes, int inst, const std::string& lb,
                                  int best, unsigned long long m, unsigned long long M,
                                  unsigned long long capacity, int geom,
@@ -249,10 +257,9 @@ struct DevpoolSnapshot {
   DevpoolStepCtl ctl;
 };
 std::vector<DevpoolSnapshot<NQNode>> nq_devpool_chain(
-    const std::vector<NQNode>& nodes, int N, int g, int finish, unsigned long long m,
-    const std::vector<unsigned long long>& windows, unsigned long long capacity,
-    const std::string& presum, int device, int split = -1, int refill = -1, int stack = -1,
-    int stack_cap = -1);
+    const std::vector<NQNode>& nodes, int N, int g, const NqFinishOpts& finisher,
+    unsigned long long m, const std::vector<unsigned long long>& windows,
+    unsigned long long capacity, const std::string& presum, int device);
 std::vector<DevpoolSnapshot<PFSPNode>> pfsp_devpool_chain(
     const std::vector<PFSPNode>& nodes, int inst, const std::string& lb, int best,
     unsigned long long m, const std::vector<unsigned long long>& windows,

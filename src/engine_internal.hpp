@@ -177,33 +177,16 @@ struct NqDevProblem {
   int per;  // N
   int lbg = 1;
   int g;
-  int finish;  // depth of the in-thread bitmask subtree finisher
-  int split;   // levels the finisher jobs are split into sub-jobs (0..2)
-  int refill;  // idle lanes at which a wave of the split / stack finisher refills (1..64)
-  int stack;      // 1: the wave-stack finisher instead of the split one
-  int stack_cap;  // its push limit per wave, < 0 = the kernel's capacity (a test knob)
+  NqFinishOpts finisher;  // resolved for this g: nq_finish_opts(g, ...)
 
-  // split < 0 / refill < 0: the engine's defaults (GATS_NQ_SPLIT, GATS_NQ_REFILL).
-  // stack < 0: the stack finisher where the split is the default too, g == 1
-  // and GATS_NQ_STACK says so; an explicit split keeps the split kernels, and
-  // so does g > 1 (the g repeats are issued per wave iteration, of which the
-  // stack schedule has far fewer: BASELINE.md "Wave-stack finisher").
-  NqDevProblem(int N, int g_, int finish_, int split_ = -1, int refill_ = -1, int stack_ = -1,
-               int stack_cap_ = -1)
-      : per(N),
-        g(g_),
-        finish(finish_),
-        split(split_ < 0 ? nq_split_default() : split_),
-        refill(refill_ < 0 ? nq_refill_default() : refill_),
-        stack(stack_ < 0 ? (split_ < 0 && g_ == 1 && nq_stack_default() == 1) : stack_ != 0),
-        stack_cap(stack_cap_) {}
+  NqDevProblem(int N, int g_, const NqFinishOpts& finisher_)
+      : per(N), g(g_), finisher(finisher_) {}
   NqDevProblem on_device(int) const { return *this; }
 
   void enqueue(const DevpoolBufs<NQNode>& b, DevCtl* cur, DevCtl* next, unsigned long long m,
                unsigned long long Mi, bool presum, hipStream_t s) const {
     const int Gi = devpool_grid(Mi, per, lbg);
-    launch_nq_x(cur, b.pool.p, b.childbuf.p, b.bc.p, b.bs.p, b.be(), per, g, finish, split,
-                refill, m, Mi, s, stack, stack_cap);
+    launch_nq_x(cur, b.pool.p, b.childbuf.p, b.bc.p, b.bs.p, b.be(), per, g, finisher, m, Mi, s);
     if (presum) launch_presum(b.bc.p, b.gsum.p, Gi, s);
     launch_gather2_nq(cur, next, b.bc.p, b.bs.p, b.be(), presum ? b.gsum.p : nullptr,
                       b.childbuf.p, b.pool.p, b.stride, Gi, m, Mi, b.capacity, s);

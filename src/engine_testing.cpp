@@ -179,25 +179,13 @@ DevpoolStepCtl devpool_step(const Problem& problem, std::vector<typename Problem
 
 }  // namespace
 
-// stack = 1 is the finisher of the default split only; stack_cap is its knob
-static void validate_nq_stack(int split, int stack, int stack_cap) {
-  if (stack > 1) throw std::invalid_argument("stack must be 0 or 1, or < 0");
-  if (stack == 1 && split >= 0)
-    throw std::invalid_argument("stack = 1 takes no explicit split");
-  if (stack_cap > NQ_STACK_CAP)
-    throw std::invalid_argument("stack_cap must be in 0.." + std::to_string(NQ_STACK_CAP) +
-                                ", or < 0");
-}
-
-DevpoolStepCtl nq_devpool_step(std::vector<NQNode>& nodes, int N, int g, int finish,
-                               unsigned long long m, unsigned long long M,
-                               unsigned long long capacity, const std::string& presum,
-                               int device, int split, int refill, int stack, int stack_cap) {
-  validate_nq_step(nodes, N, g, finish, m, M, capacity, presum);  // before any HIP call
-  if (split > NQ_SPLIT_MAX) throw std::invalid_argument("split must be in 0..2, or < 0");
-  if (refill == 0 || refill > 64) throw std::invalid_argument("refill must be in 1..64, or < 0");
-  validate_nq_stack(split, stack, stack_cap);
-  return devpool_step(NqDevProblem(N, g, finish, split, refill, stack, stack_cap), nodes,
+DevpoolStepCtl nq_devpool_step(std::vector<NQNode>& nodes, int N, int g,
+                               const NqFinishOpts& finisher, unsigned long long m,
+                               unsigned long long M, unsigned long long capacity,
+                               const std::string& presum, int device) {
+  // before any HIP call
+  validate_nq_step(nodes, N, g, finisher.finish, m, M, capacity, presum);
+  return devpool_step(NqDevProblem(N, g, nq_finish_opts(g, finisher)), nodes,
                       /*best=*/0, m, M, capacity, presum_mode(presum), device);
 }
 
@@ -318,16 +306,15 @@ std::vector<DevpoolSnapshot<typename Problem::Node>> devpool_chain(
 }  // namespace
 
 std::vector<DevpoolSnapshot<NQNode>> nq_devpool_chain(
-    const std::vector<NQNode>& nodes, int N, int g, int finish, unsigned long long m,
-    const std::vector<unsigned long long>& windows, unsigned long long capacity,
-    const std::string& presum, int device, int split, int refill, int stack, int stack_cap) {
-  validate_nq_step(nodes, N, g, finish, m, 1, capacity, presum);  // before any HIP call
-  if (split > NQ_SPLIT_MAX) throw std::invalid_argument("split must be in 0..2, or < 0");
-  if (refill == 0 || refill > 64) throw std::invalid_argument("refill must be in 1..64, or < 0");
-  validate_nq_stack(split, stack, stack_cap);
+    const std::vector<NQNode>& nodes, int N, int g, const NqFinishOpts& finisher,
+    unsigned long long m, const std::vector<unsigned long long>& windows,
+    unsigned long long capacity, const std::string& presum, int device) {
+  // before any HIP call
+  validate_nq_step(nodes, N, g, finisher.finish, m, 1, capacity, presum);
+  const NqFinishOpts opts = nq_finish_opts(g, finisher);
   validate_chain_windows(windows, N, capacity);
-  return devpool_chain(NqDevProblem(N, g, finish, split, refill, stack, stack_cap), nodes,
-                       /*best=*/0, m, windows, capacity, presum_mode(presum), device);
+  return devpool_chain(NqDevProblem(N, g, opts), nodes, /*best=*/0, m, windows, capacity,
+                       presum_mode(presum), device);
 }
 
 std::vector<DevpoolSnapshot<PFSPNode>> pfsp_devpool_chain(
@@ -483,7 +470,8 @@ DevpoolLoopOut<NQNode> nq_devpool_loop(const std::vector<NQNode>& nodes, int N, 
   validate_nq_step(nodes, N, g, finish, m, chunk, capacity, "auto");
   validate_devpool_loop(nodes.size(), chunk, capacity, max_batches);
   if (m > (1ull << 30)) throw std::invalid_argument("m must be <= 2^30");
-  return devpool_loop_traced(NqDevProblem(N, g, finish), nodes, /*best0=*/0, m, chunk,
+  return devpool_loop_traced(NqDevProblem(N, g, nq_finish_opts(g, {finish})), nodes,
+                             /*best0=*/0, m, chunk,
                              capacity, graph, max_batches, nullptr, -1, 0, device);
 }
 
@@ -591,7 +579,8 @@ std::vector<DevpoolLoopOut<NQNode>> nq_devpool_share(
   validate_devpool_loop(nodes.size(), chunk, capacity, max_batches);
   validate_devpool_share(threads, static_cast<long long>(donate_floor), await_idle_ms);
   if (m > (1ull << 30)) throw std::invalid_argument("m must be <= 2^30");
-  return devpool_share_traced(NqDevProblem(N, g, finish), nodes, /*best0=*/0, m, chunk,
+  return devpool_share_traced(NqDevProblem(N, g, nq_finish_opts(g, {finish})), nodes,
+                              /*best0=*/0, m, chunk,
                               capacity, max_batches, nullptr, threads, donate_floor,
                               await_idle_ms, device);
 }

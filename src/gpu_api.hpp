@@ -56,6 +56,17 @@ struct PfspDevTables {
   const int32_t* min_heads;          // [machines]
 };
 
+// The knobs of k_nq_x's subtree finisher. A caller leaves < 0 what it does not
+// set; nq_finish_opts (engine_gpu.hpp) validates its values and fills in the
+// GATS_NQ_* defaults. NqDevProblem and launch_nq_x take the resolved struct,
+// whose ranges are the ones given here.
+struct NqFinishOpts {
+  int finish;          // levels from the bottom that are counted in-kernel (<= 8)
+  int split = -1;      // levels the finisher jobs are split into sub-jobs (0..2)
+  int refill = -1;     // idle lanes at which a wave of the split / stack finisher refills (1..64)
+  int stack = -1;      // 1: the wave-stack finisher instead of the split one
+  int stack_cap = -1;  // its push limit per wave (0..NQ_STACK_CAP; below it is a test knob)
+};
 
 
 // Launchers implemented in kernels.hip.
@@ -83,9 +94,8 @@ int devpool_grid(unsigned long long M, int per, int lbk);
 int devpool_stride(int lbk);
 void launch_nq_x(const DevCtl* ctl, const NQNode* pool, NQNode* childbuf,
                  uint32_t* blockCounts, unsigned long long* blockSols,
-                 unsigned long long* blockExtra, int N, int g, int finish, int split,
-                 int refill, unsigned long long m, unsigned long long M, hipStream_t s,
-                 int stack = 0, int stack_cap = -1);
+                 unsigned long long* blockExtra, int N, int g, const NqFinishOpts& o,
+                 unsigned long long m, unsigned long long M, hipStream_t s);
 void launch_pfsp_x(DevCtl* ctl, const PFSPNode* pool, PFSPNode* childbuf, uint32_t* bc,
                    unsigned long long* bs, int jobs, int machines, int lbk,
                    const PfspDevTables& tb, unsigned long long m, unsigned long long M,

@@ -674,29 +674,315 @@ __device__ inline unsigned long long derive_chunk(const DevCtl* ctl, unsigned lo
 // in slot order into an LDS queue (wave ballots + a 16-entry count table: no
 // atomics, so the order is the same in every run). Phase C drains the queue
 // in ONE loop per lane (nq_flat_run), so a wave's lanes stay busy whatever
-// depth or job each of them is in. SPLIT == 0: thread t walks jobs t, t + 256,
-// ... SPLIT == 1 / 2: every job is first split one / two levels into sub-jobs
+// depth or job each of them is in. The kernel is classify, drain, emit; the
+// drain is one of three functions (NqDrain, chosen by launch_nq_x), each of
+// which returns the lane's counts.
+// flat: thread t walks jobs t, t + 256, ...
+// split1 / split2: every job is first split one / two levels into sub-jobs
 // (nq_finish.hpp), the sub-jobs go into a second LDS queue of NQ_SPLIT_QCAP
 // entries (ranked by a block scan, filled and drained in rounds when they do
 // not all fit), and a wave that has `refill` idle lanes (or only idle lanes)
 // hands all of them the next unclaimed entries from an LDS counter
 // (nq_refill_now): which lane walks what varies, the sums do not.
-// SPLIT == NQ_X_STACK: the wave-stack finisher (nq_finish.hpp). A lane owns a
+// stack: the wave-stack finisher (nq_finish.hpp). A lane owns a
 // row and never backtracks; children with an inner row below them go onto the
 // wave's own LDS stack of NQ_STACK_CAP entries, idle lanes take them off it or
 // draw whole jobs from jobq through one LDS counter. No split pass, no sub-job
-// queue, no block barrier inside phase C. stack_cap (<= NQ_STACK_CAP) is the
+// queue, no block barrier inside the drain. stack_cap (<= NQ_STACK_CAP) is the
 // height past which children are walked instead of pushed (a test knob).
-constexpr int NQ_X_STACK = 3;
-template <bool G1, int SPLIT>
+enum class NqDrain { flat, split1, split2, stack };
+
+// 16-byte aligned wherever it lands behind a drain's struct: the 16 jobcnt
+// words are then read with four 128-bit LDS reads (measured: BASELINE.md
+// "Finisher refactor").
+struct alignas(16) NqTileLds {
+  NQNode s[EMIT_TILE / 4 + 2];        // staged parents; N >= 4 (engine falls back below)
+  uint64_t pmask[EMIT_TILE / 4 + 2];  // per-parent cols/d1/d2 (nq_pmask_pack)
+  uint16_t jobq[EMIT_TILE];           // finisher jobs: nq_job_ref(local parent id, column)
+  uint32_t jobcnt[(EMIT_TILE / BLOCK) * (BLOCK / 64)];  // jobs per (j, wave)
+};
+struct NqStackLds {
+  uint64_t stk[BLOCK / 64][NQ_STACK_CAP];  // one node stack per wave
+  uint32_t jhead;                          // next undrawn job
+};
+struct NqSplitLds {
+  uint32_t subq[NQ_SPLIT_QCAP];    // the round's sub-jobs (nq_sub_encode)
+  uint16_t joboff[EMIT_TILE + 2];  // the jobs' exclusive sub-job offsets
+  uint32_t qhead;                  // next unclaimed entry
+};
+static_assert(MAX_JOBS <= 32 && (EMIT_TILE / 4 + 2) * 32 <= 65536, "jobq entry is 16-bit");
+static_assert(EMIT_TILE * NQ_SPLIT_FANOUT_MAX < 65536, "sub-job offsets are 16-bit");
+// A block's LDS. The drain's arrays come first: the stack / queue that its
+// inner loop indexes sits at LDS address 0 and needs no base register.
+template <NqDrain D>
+struct NqLds {
+  NqSplitLds drain;
+  NqTileLds tile;
+};
+template <>
+struct NqLds<NqDrain::stack> {
+  NqStackLds drain;
+  NqTileLds tile;
+};
+template <>
+struct NqLds<NqDrain::flat> {
+  NqTileLds tile;
+};
+// With block_excl_scan's and block_reduce_u64's scratch and the padding
+// between the three, a block's LDS must leave eight blocks per CU.
+template <NqDrain D>
+constexpr size_t nq_x_lds_bytes =
+    sizeof(NqLds<D>) + 4 * sizeof(uint32_t) + 4 * sizeof(unsigned long long) + 16;
+
+// What a lane's drain counted. nodes: the candidates of the rows the split
+// pass enumerated (the split drain alone).
+// 32-bit per-lane counters: a block's whole queue is at most 1024 jobs of
+// <= 109,600 nodes each, below 2^32, whichever lane walks what
+struct NqDrained {
+  uint32_t tree = 0, sol = 0;
+  unsigned long long nodes = 0;
+};
+
+// job ref -> the child's masks, seen from the row below it (as phase A
+// steps them); returns that row. One LDS read: the parent's packed masks.
+__device__ inline int nq_tile_job(const NqTileLds& t, uint32_t e, uint32_t msk, uint32_t& jc,
+                                  uint32_t& jd1, uint32_t& jd2) {
+  return nq_job_state(t.pmask[nq_job_parent(e)], e, msk, jc, jd1, jd2);
+}
+
+// Phase A: one thread per staged parent computes its packed masks.
+__device__ inline void nq_tile_masks(NqTileLds& t, int nblk, int N, uint32_t msk) {
+  for (int pi = threadIdx.x; pi < nblk; pi += blockDim.x) {
+    const NQNode& p = t.s[pi];
+    uint32_t cols = 0, d1 = 0, d2 = 0;
+    const int depth = p.depth;
+    for (int i = 0; i < depth && i < N; i++) {
+      const uint32_t b = 1u << p.board[i];
+      cols |= b;
+      d1 = ((d1 | b) << 1) & msk;
+      d2 = (d2 | b) >> 1;
+    }
+    t.pmask[pi] = nq_pmask_pack(cols, d1, d2);
+  }
+}
+
+// Job queue: the slots labelled 2 go into t.jobq in slot order; slot
+// j * 256 + threadIdx.x ranks as (j, wave, lane). Returns the number of jobs.
+// Two block barriers; the queue is complete after the second.
+__device__ inline uint32_t nq_tile_rank_jobs(NqTileLds& t, const uint8_t (&lab)[EMIT_TILE / BLOCK],
+                                             const uint16_t (&lpid)[EMIT_TILE / BLOCK],
+                                             const uint8_t (&lcol)[EMIT_TILE / BLOCK]) {
+  const int lane = threadIdx.x & 63;
+  const int wid = threadIdx.x >> 6;
+  uint32_t rank[EMIT_TILE / BLOCK];
+#pragma unroll
+  for (int j = 0; j < EMIT_TILE / BLOCK; j++) {
+    const unsigned long long bal = __ballot(lab[j] == 2);
+    rank[j] = static_cast<uint32_t>(__popcll(bal & ((1ull << lane) - 1ull)));
+    if (lane == 0) t.jobcnt[j * (BLOCK / 64) + wid] = static_cast<uint32_t>(__popcll(bal));
+  }
+  __syncthreads();
+  uint32_t njobs = 0;
+#pragma unroll
+  for (int i = 0; i < (EMIT_TILE / BLOCK) * (BLOCK / 64); i++) {
+    if (i % (BLOCK / 64) == wid) rank[i / (BLOCK / 64)] += njobs;
+    njobs += t.jobcnt[i];
+  }
+#pragma unroll
+  for (int j = 0; j < EMIT_TILE / BLOCK; j++)
+    if (lab[j] == 2) t.jobq[rank[j]] = static_cast<uint16_t>(nq_job_ref(lpid[j], lcol[j]));
+  __syncthreads();
+  return njobs;
+}
+
+// Flat drain: one flat loop per lane over its strided share of the queue.
+template <bool G1>
+__device__ inline NqDrained nq_drain_flat(const NqTileLds& t, uint32_t njobs, uint32_t msk, int N,
+                                          int g) {
+  NqFlat<NQ_FLAT_LEVELS_DEV> st;
+  st.tree = 0;
+  st.sol = 0;
+  uint32_t q = threadIdx.x;
+  nq_flat_run<NQ_FLAT_LEVELS_DEV, G1>(
+      st,
+      [&](NqFlat<NQ_FLAT_LEVELS_DEV>& w) {
+        if (q >= njobs) return false;
+        const uint32_t e = t.jobq[q];
+        q += BLOCK;
+        uint32_t jc, jd1, jd2;
+        const int row = nq_tile_job(t, e, msk, jc, jd1, jd2);
+        w.template load<G1>(jc, jd1, jd2, row, N, msk, g);
+        return true;
+      },
+      msk, g);
+  return {st.tree, st.sol, 0};
+}
+
+// Stack drain. One block barrier (after the job counter's reset).
+template <bool G1>
+__device__ inline NqDrained nq_drain_stack(const NqTileLds& t, NqStackLds& d, uint32_t njobs,
+                                           uint32_t msk, int N, int g, int refill,
+                                           int stack_cap) {
+  const int lane = threadIdx.x & 63;
+  const int wid = threadIdx.x >> 6;
+  if (threadIdx.x == 0) d.jhead = 0;
+  __syncthreads();
+  uint64_t* const my = d.stk[wid];  // this wave's stack; no other wave touches it
+  const unsigned long long lt = (1ull << lane) - 1ull;
+  const uint32_t T = static_cast<uint32_t>(refill);
+  const uint32_t cap = static_cast<uint32_t>(stack_cap);  // <= NQ_STACK_CAP (launch_nq_x)
+  NqRow r = {0, 0, 0, 0, 0, 0, 0};
+  uint32_t sp = 0;   // wave-uniform: ballots and the broadcast counter alone move it
+  bool more = true;  // wave-uniform
+  unsigned long long im = ~0ull;  // every lane starts idle, so the wave starts by acting
+  uint32_t nidle = 64u;
+  // Why it ends: see nq_stack_act (nq_finish.hpp). The iterations that only
+  // step and push are an inner loop of their own; the fetch is behind the
+  // scalar branch nq_stack_act.
+  for (;;) {
+    if (nq_stack_done(nidle, 64u, sp, more)) break;
+    const bool idle = r.cand == 0;
+    const uint32_t rank = static_cast<uint32_t>(__popcll(im & lt));
+    const uint32_t take = nq_stack_take(nidle, sp);
+    // rank < take <= sp: my[sp - 1 - rank] is inside [0, sp)
+    if (idle && rank < take) nq_row_load_entry(r, my[sp - 1u - rank], msk);
+    sp -= take;
+    if (more && nidle > take) {
+      const uint32_t rem = nq_stack_draw(nidle - take, njobs, BLOCK / 64);
+      uint32_t got = 0;
+      if (lane == 0) got = atomicAdd(&d.jhead, rem);
+      got = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(got)));
+      more = !nq_refill_drains(got, rem, njobs);
+      const uint32_t qi = got + rank - take;
+      // qi < njobs <= EMIT_TILE: inside jobq
+      if (idle && rank >= take && rank - take < rem && qi < njobs) {
+        uint32_t jc, jd1, jd2;
+        const int row = nq_tile_job(t, t.jobq[qi], msk, jc, jd1, jd2);
+        nq_row_load_job<G1>(r, jc, jd1, jd2, row, N, msk, g);
+      }
+    }
+    do {
+      uint32_t nc, n1, n2;
+      const bool push = nq_row_step<G1>(r, msk, g, nc, n1, n2);  // idle lanes pass through
+      if (nq_stack_can_push(sp, 64u, cap)) {  // scalar: sp + 64 <= cap <= NQ_STACK_CAP
+        const unsigned long long pm = __builtin_amdgcn_ballot_w64(push);
+        if (push)
+          my[sp + static_cast<uint32_t>(__popcll(pm & lt))] = nq_entry_pack(nc, n1, n2, r.h - 1u);
+        sp += static_cast<uint32_t>(__popcll(pm));
+      } else if (push) {
+        nq_row_walk<G1>(r, nc, n1, n2, N, msk, g);
+      }
+      im = __builtin_amdgcn_ballot_w64(r.cand == 0);
+      nidle = static_cast<uint32_t>(__popcll(im));
+    } while (!nq_stack_act(nidle, 64u, T, sp, more));
+  }
+  return {r.tree, r.sol, 0};
+}
+
+// Split drain, S levels. Its barriers (the count pass's scans, one after the
+// offsets, two per round) are all at block-uniform places.
+template <bool G1, int S>
+__device__ inline NqDrained nq_drain_split(const NqTileLds& t, NqSplitLds& d, uint32_t njobs,
+                                           uint32_t msk, int N, int g, int refill) {
+  const int lane = threadIdx.x & 63;
+  NqDrained out;
+  // count pass: thread t counts the sub-jobs of jobs t, t + 256, ...
+  // (and the nodes of the rows it enumerates); a block scan per row of 256
+  // jobs turns the counts into queue offsets, in job order.
+  uint32_t run = 0;
+  for (uint32_t q0 = 0; q0 < njobs; q0 += BLOCK) {  // block-uniform trip count
+    const uint32_t q = q0 + threadIdx.x;
+    uint32_t n = 0;
+    if (q < njobs) {
+      uint32_t jc, jd1, jd2, nodes = 0;
+      const int row = nq_tile_job(t, t.jobq[q], msk, jc, jd1, jd2);
+      n = nq_split_job<G1, false>(jc, jd1, jd2, nq_split_levels(S, N - row), msk, g, nodes,
+                                  [](uint32_t, uint32_t, uint32_t) {});
+      out.nodes += nodes;
+    }
+    uint32_t tot;
+    const uint32_t pre = block_excl_scan(n, tot);
+    if (q < njobs) d.joboff[q] = static_cast<uint16_t>(run + pre);
+    run += tot;
+  }
+  if (threadIdx.x == 0) d.joboff[njobs] = static_cast<uint16_t>(run);
+  __syncthreads();
+  // rounds: the longest run of jobs whose sub-jobs fit the queue
+  // is written out and drained. A wave refills all of its idle lanes at
+  // once when `refill` of them are idle (nq_refill_now: one LDS add per
+  // refill, two LDS reads per lane); otherwise a scalar branch skips the
+  // fetch.
+  NqFlat<NQ_FLAT_LEVELS_DEV> st;
+  st.tree = 0;
+  st.sol = 0;
+  const unsigned long long lt = (1ull << lane) - 1ull;
+  const uint32_t T = static_cast<uint32_t>(refill);
+  for (uint32_t jb = 0; jb < njobs;) {  // block-uniform: je comes from LDS alone
+    const uint32_t je = nq_round_end(d.joboff, jb, njobs, NQ_SPLIT_QCAP);
+    const uint32_t base = d.joboff[jb];
+    const uint32_t nsub = d.joboff[je] - base;
+    for (uint32_t q = jb + threadIdx.x; q < je; q += BLOCK) {
+      const uint32_t e = t.jobq[q];
+      uint32_t jc, jd1, jd2, nodes = 0;
+      const int row = nq_tile_job(t, e, msk, jc, jd1, jd2);
+      uint32_t w = d.joboff[q] - base;
+      nq_split_job<true, true>(jc, jd1, jd2, nq_split_levels(S, N - row), msk, 1, nodes,
+                               [&](uint32_t nc, uint32_t c1, uint32_t c2) {
+                                 d.subq[w++] = nq_sub_encode(e, nc, c1, c2);
+                               });
+    }
+    if (threadIdx.x == 0) d.qhead = 0;
+    __syncthreads();
+    // Every lane of the wave stays in the loop until the wave leaves it
+    // (the ballots need them all): `drained`, the refill decision and the
+    // exit are wave-uniform. Why it ends: see nq_refill_now (nq_finish.hpp).
+    // The iterations that only step are an inner loop of their own: one
+    // ballot, one scalar compare against nq_refill_level, no fetch code.
+    bool drained = false;
+    st.cand = 0;
+    st.stack = 0;
+    bool idle = true;                  // every lane starts without a walk,
+    unsigned long long im = ~0ull;     // so the all-idle rule starts the wave
+    uint32_t nidle = 64u;
+    for (;;) {
+      if (nq_wave_done(nidle, 64u, drained)) break;
+      // here nq_refill_now(nidle, 64, T, drained) holds
+      uint32_t got = 0;
+      if (lane == 0) got = atomicAdd(&d.qhead, nidle);
+      got = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(got)));
+      drained = nq_refill_drains(got, nidle, nsub);
+      const uint32_t qi = got + static_cast<uint32_t>(__popcll(im & lt));
+      if (idle && qi < nsub) {  // qi < nsub <= NQ_SPLIT_QCAP: inside subq
+        const uint32_t e = d.subq[qi];
+        uint32_t jc, jd1, jd2;
+        const int row = nq_tile_job(t, nq_sub_ref(e), msk, jc, jd1, jd2);
+        nq_sub_load<G1>(st, e, jc, jd1, jd2, row, N, msk, g);
+      }
+      const uint32_t level = nq_refill_level(64u, T, drained);
+      do {
+        if (st.cand == 0 && st.stack > 1) st.pop(msk);
+        if (st.cand) st.template take<G1>(msk, g);
+        idle = nq_lane_idle(st.cand, st.stack);
+        im = __builtin_amdgcn_ballot_w64(idle);
+        nidle = static_cast<uint32_t>(__popcll(im));
+      } while (nidle < level);
+    }
+    __syncthreads();  // the next round rewrites subq and qhead
+    jb = je;
+  }
+  out.tree = st.tree;
+  out.sol = st.sol;
+  return out;
+}
+
+template <bool G1, NqDrain D>
 __global__ void k_nq_x(const DevCtl* ctl, const NQNode* pool, NQNode* childbuf,
                        uint32_t* blockCounts, unsigned long long* blockSols,
                        unsigned long long* blockExtra, int N, int g, int finish, int refill,
                        int stack_cap, unsigned long long m, unsigned long long M) {
-  __shared__ NQNode s[EMIT_TILE / 4 + 2];  // N >= 4 (engine falls back below)
-  __shared__ uint64_t pmask[EMIT_TILE / 4 + 2];  // per-parent cols/d1/d2 (nq_pmask_pack)
-  __shared__ uint16_t jobq[EMIT_TILE];  // finisher jobs: nq_job_ref(local parent id, column)
-  __shared__ uint32_t jobcnt[(EMIT_TILE / BLOCK) * (BLOCK / 64)];  // jobs per (j, wave)
+  __shared__ NqLds<D> lds;
+  static_assert(nq_x_lds_bytes<D> <= 20480, "k_nq_x's LDS must leave eight blocks per CU");
+  NqTileLds& tile = lds.tile;
   const unsigned long long c = derive_chunk(ctl, m, M);
   // child indices fit u32: the engine enforces M * branching <= 2^31
   const uint32_t total = static_cast<uint32_t>(c * N);
@@ -713,23 +999,9 @@ __global__ void k_nq_x(const DevCtl* ctl, const NQNode* pool, NQNode* childbuf,
     const uint32_t msk = (1u << N) - 1u;
     uint32_t c1 = c0 + EMIT_TILE;
     if (c1 > total) c1 = total;
-    first = stage_range(parents, c0, c1, N, s);
+    first = stage_range(parents, c0, c1, N, tile.s);
     __syncthreads();
-    {  // phase A: one thread per staged parent
-      const int nblk = static_cast<int>((c1 - 1) / N - first + 1);
-      for (int pi = threadIdx.x; pi < nblk; pi += blockDim.x) {
-        const NQNode& p = s[pi];
-        uint32_t cols = 0, d1 = 0, d2 = 0;
-        const int depth = p.depth;
-        for (int i = 0; i < depth && i < N; i++) {
-          const uint32_t b = 1u << p.board[i];
-          cols |= b;
-          d1 = ((d1 | b) << 1) & msk;
-          d2 = (d2 | b) >> 1;
-        }
-        pmask[pi] = nq_pmask_pack(cols, d1, d2);
-      }
-    }
+    nq_tile_masks(tile, static_cast<int>((c1 - 1) / N - first + 1), N, msk);  // phase A
     __syncthreads();
 #pragma unroll
     for (int j = 0; j < EMIT_TILE / BLOCK; j++) {  // phase B: classify the child slots
@@ -739,13 +1011,13 @@ __global__ void k_nq_x(const DevCtl* ctl, const NQNode* pool, NQNode* childbuf,
         const int k = static_cast<int>(t - pid * N);
         lpid[j] = static_cast<uint16_t>(pid - first);
         lk[j] = static_cast<uint8_t>(k);
-        const NQNode& p = s[pid - first];
+        const NQNode& p = tile.s[pid - first];
         const int depth = p.depth;
         if (depth == N) {
           sols += (k == 0);  // leaf parent counted once (nqueens_chpl.chpl:78-80)
         } else if (k >= depth) {
           uint32_t pc, pd1, pd2;
-          nq_pmask_unpack(pmask[pid - first], pc, pd1, pd2);
+          nq_pmask_unpack(tile.pmask[pid - first], pc, pd1, pd2);
           const uint32_t occ = pc | pd1 | pd2;
           lcol[j] = p.board[k];
           const uint32_t b = 1u << lcol[j];
@@ -767,211 +1039,19 @@ __global__ void k_nq_x(const DevCtl* ctl, const NQNode* pool, NQNode* childbuf,
         cnt += (lab[j] == 1);
       }
     }
-    // job queue: slot j * 256 + threadIdx.x ranks as (j, wave, lane)
-    const int lane = threadIdx.x & 63;
-    const int wid = threadIdx.x >> 6;
-    uint32_t rank[EMIT_TILE / BLOCK];
-#pragma unroll
-    for (int j = 0; j < EMIT_TILE / BLOCK; j++) {
-      const unsigned long long bal = __ballot(lab[j] == 2);
-      rank[j] = static_cast<uint32_t>(__popcll(bal & ((1ull << lane) - 1ull)));
-      if (lane == 0) jobcnt[j * (BLOCK / 64) + wid] = static_cast<uint32_t>(__popcll(bal));
-    }
-    __syncthreads();
-    uint32_t njobs = 0;
-#pragma unroll
-    for (int i = 0; i < (EMIT_TILE / BLOCK) * (BLOCK / 64); i++) {
-      if (i % (BLOCK / 64) == wid) rank[i / (BLOCK / 64)] += njobs;
-      njobs += jobcnt[i];
-    }
-#pragma unroll
-    for (int j = 0; j < EMIT_TILE / BLOCK; j++)
-      if (lab[j] == 2) jobq[rank[j]] = static_cast<uint16_t>(nq_job_ref(lpid[j], lcol[j]));
-    __syncthreads();
-    // phase C: one flat loop per lane over its share of the queue
-    static_assert(MAX_JOBS <= 32 && (EMIT_TILE / 4 + 2) * 32 <= 65536, "jobq entry is 16-bit");
-    NqFlat<NQ_FLAT_LEVELS_DEV> st;
-    st.tree = 0;
-    st.sol = 0;
-    // job ref -> the child's masks, seen from the row below it (as phase A
-    // steps them); returns that row. One LDS read: the parent's packed masks.
-    auto job_state = [&](uint32_t e, uint32_t& jc, uint32_t& jd1, uint32_t& jd2) {
-      return nq_job_state(pmask[nq_job_parent(e)], e, msk, jc, jd1, jd2);
-    };
-    if constexpr (SPLIT == 0) {
-      uint32_t q = threadIdx.x;
-      nq_flat_run<NQ_FLAT_LEVELS_DEV, G1>(
-          st,
-          [&](NqFlat<NQ_FLAT_LEVELS_DEV>& w) {
-            if (q >= njobs) return false;
-            const uint32_t e = jobq[q];
-            q += BLOCK;
-            uint32_t jc, jd1, jd2;
-            const int row = job_state(e, jc, jd1, jd2);
-            w.template load<G1>(jc, jd1, jd2, row, N, msk, g);
-            return true;
-          },
-          msk, g);
-    } else if constexpr (SPLIT == NQ_X_STACK) {
-      __shared__ uint64_t stk[BLOCK / 64][NQ_STACK_CAP];
-      __shared__ uint32_t jhead;
-      static_assert(sizeof(s) + sizeof(pmask) + sizeof(jobq) + sizeof(jobcnt) + sizeof(stk) +
-                            sizeof(jhead) + 4 * sizeof(uint32_t) +
-                            4 * sizeof(unsigned long long) + 16 <=
-                        20480,
-                    "k_nq_x's LDS (with the scan / reduce scratch and padding) must leave "
-                    "eight blocks per CU");
-      if (threadIdx.x == 0) jhead = 0;
-      __syncthreads();
-      uint64_t* const my = stk[wid];  // this wave's stack; no other wave touches it
-      const unsigned long long lt = (1ull << lane) - 1ull;
-      const uint32_t T = static_cast<uint32_t>(refill);
-      const uint32_t cap = static_cast<uint32_t>(stack_cap);  // <= NQ_STACK_CAP (launch_nq_x)
-      NqRow r = {0, 0, 0, 0, 0, 0, 0};
-      uint32_t sp = 0;   // wave-uniform: ballots and the broadcast counter alone move it
-      bool more = true;  // wave-uniform
-      unsigned long long im = ~0ull;  // every lane starts idle, so the wave starts by acting
-      uint32_t nidle = 64u;
-      // Why it ends: see nq_stack_act (nq_finish.hpp). The iterations that only
-      // step and push are an inner loop of their own; the fetch is behind the
-      // scalar branch nq_stack_act.
-      for (;;) {
-        if (nq_stack_done(nidle, 64u, sp, more)) break;
-        const bool idle = r.cand == 0;
-        const uint32_t rank = static_cast<uint32_t>(__popcll(im & lt));
-        const uint32_t take = nq_stack_take(nidle, sp);
-        // rank < take <= sp: my[sp - 1 - rank] is inside [0, sp)
-        if (idle && rank < take) nq_row_load_entry(r, my[sp - 1u - rank], msk);
-        sp -= take;
-        if (more && nidle > take) {
-          const uint32_t rem = nq_stack_draw(nidle - take, njobs, BLOCK / 64);
-          uint32_t got = 0;
-          if (lane == 0) got = atomicAdd(&jhead, rem);
-          got = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(got)));
-          more = !nq_refill_drains(got, rem, njobs);
-          const uint32_t qi = got + rank - take;
-          // qi < njobs <= EMIT_TILE: inside jobq
-          if (idle && rank >= take && rank - take < rem && qi < njobs) {
-            uint32_t jc, jd1, jd2;
-            const int row = job_state(jobq[qi], jc, jd1, jd2);
-            nq_row_load_job<G1>(r, jc, jd1, jd2, row, N, msk, g);
-          }
-        }
-        do {
-          uint32_t nc, n1, n2;
-          const bool push = nq_row_step<G1>(r, msk, g, nc, n1, n2);  // idle lanes pass through
-          if (nq_stack_can_push(sp, 64u, cap)) {  // scalar: sp + 64 <= cap <= NQ_STACK_CAP
-            const unsigned long long pm = __builtin_amdgcn_ballot_w64(push);
-            if (push)
-              my[sp + static_cast<uint32_t>(__popcll(pm & lt))] =
-                  nq_entry_pack(nc, n1, n2, r.h - 1u);
-            sp += static_cast<uint32_t>(__popcll(pm));
-          } else if (push) {
-            nq_row_walk<G1>(r, nc, n1, n2, N, msk, g);
-          }
-          im = __builtin_amdgcn_ballot_w64(r.cand == 0);
-          nidle = static_cast<uint32_t>(__popcll(im));
-        } while (!nq_stack_act(nidle, 64u, T, sp, more));
-      }
-      st.tree = r.tree;
-      st.sol = r.sol;
+    const uint32_t njobs = nq_tile_rank_jobs(tile, lab, lpid, lcol);
+    NqDrained d;  // phase C
+    if constexpr (D == NqDrain::flat) {
+      d = nq_drain_flat<G1>(tile, njobs, msk, N, g);
+    } else if constexpr (D == NqDrain::stack) {
+      d = nq_drain_stack<G1>(tile, lds.drain, njobs, msk, N, g, refill, stack_cap);
     } else {
-      // phase C1, split: thread t counts the sub-jobs of jobs t, t + 256, ...
-      // (and the nodes of the rows it enumerates); a block scan per row of 256
-      // jobs turns the counts into queue offsets, in job order.
-      static_assert(EMIT_TILE * NQ_SPLIT_FANOUT_MAX < 65536, "sub-job offsets are 16-bit");
-      __shared__ uint16_t joboff[EMIT_TILE + 2];
-      __shared__ uint32_t subq[NQ_SPLIT_QCAP];
-      __shared__ uint32_t qhead;
-      uint32_t run = 0;
-      for (uint32_t q0 = 0; q0 < njobs; q0 += BLOCK) {  // block-uniform trip count
-        const uint32_t q = q0 + threadIdx.x;
-        uint32_t n = 0;
-        if (q < njobs) {
-          uint32_t jc, jd1, jd2, nodes = 0;
-          const int row = job_state(jobq[q], jc, jd1, jd2);
-          n = nq_split_job<G1, false>(jc, jd1, jd2, nq_split_levels(SPLIT, N - row), msk, g,
-                                      nodes, [](uint32_t, uint32_t, uint32_t) {});
-          extra += nodes;
-        }
-        uint32_t tot;
-        const uint32_t pre = block_excl_scan(n, tot);
-        if (q < njobs) joboff[q] = static_cast<uint16_t>(run + pre);
-        run += tot;
-      }
-      if (threadIdx.x == 0) joboff[njobs] = static_cast<uint16_t>(run);
-      __syncthreads();
-      // phase C2, rounds: the longest run of jobs whose sub-jobs fit the queue
-      // is written out and drained. A wave refills all of its idle lanes at
-      // once when `refill` of them are idle (nq_refill_now: one LDS add per
-      // refill, two LDS reads per lane); otherwise a scalar branch skips the
-      // fetch.
-      static_assert(sizeof(s) + sizeof(pmask) + sizeof(jobq) + sizeof(jobcnt) + sizeof(joboff) +
-                            sizeof(subq) + sizeof(qhead) + 4 * sizeof(uint32_t) +
-                            4 * sizeof(unsigned long long) + 16 <=
-                        20480,
-                    "k_nq_x's LDS (with the scan / reduce scratch and padding) must leave "
-                    "eight blocks per CU");
-      const unsigned long long lt = (1ull << lane) - 1ull;
-      const uint32_t T = static_cast<uint32_t>(refill);
-      for (uint32_t jb = 0; jb < njobs;) {  // block-uniform: je comes from LDS alone
-        const uint32_t je = nq_round_end(joboff, jb, njobs, NQ_SPLIT_QCAP);
-        const uint32_t base = joboff[jb];
-        const uint32_t nsub = joboff[je] - base;
-        for (uint32_t q = jb + threadIdx.x; q < je; q += BLOCK) {
-          const uint32_t e = jobq[q];
-          uint32_t jc, jd1, jd2, nodes = 0;
-          const int row = job_state(e, jc, jd1, jd2);
-          uint32_t w = joboff[q] - base;
-          nq_split_job<true, true>(jc, jd1, jd2, nq_split_levels(SPLIT, N - row), msk, 1, nodes,
-                                   [&](uint32_t nc, uint32_t c1, uint32_t c2) {
-                                     subq[w++] = nq_sub_encode(e, nc, c1, c2);
-                                   });
-        }
-        if (threadIdx.x == 0) qhead = 0;
-        __syncthreads();
-        // Every lane of the wave stays in the loop until the wave leaves it
-        // (the ballots need them all): `drained`, the refill decision and the
-        // exit are wave-uniform. Why it ends: see nq_refill_now (nq_finish.hpp).
-        // The iterations that only step are an inner loop of their own: one
-        // ballot, one scalar compare against nq_refill_level, no fetch code.
-        bool drained = false;
-        st.cand = 0;
-        st.stack = 0;
-        bool idle = true;                  // every lane starts without a walk,
-        unsigned long long im = ~0ull;     // so the all-idle rule starts the wave
-        uint32_t nidle = 64u;
-        for (;;) {
-          if (nq_wave_done(nidle, 64u, drained)) break;
-          // here nq_refill_now(nidle, 64, T, drained) holds
-          uint32_t got = 0;
-          if (lane == 0) got = atomicAdd(&qhead, nidle);
-          got = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(got)));
-          drained = nq_refill_drains(got, nidle, nsub);
-          const uint32_t qi = got + static_cast<uint32_t>(__popcll(im & lt));
-          if (idle && qi < nsub) {  // qi < nsub <= NQ_SPLIT_QCAP: inside subq
-            const uint32_t e = subq[qi];
-            uint32_t jc, jd1, jd2;
-            const int row = job_state(nq_sub_ref(e), jc, jd1, jd2);
-            nq_sub_load<G1>(st, e, jc, jd1, jd2, row, N, msk, g);
-          }
-          const uint32_t level = nq_refill_level(64u, T, drained);
-          do {
-            if (st.cand == 0 && st.stack > 1) st.pop(msk);
-            if (st.cand) st.template take<G1>(msk, g);
-            idle = nq_lane_idle(st.cand, st.stack);
-            im = __builtin_amdgcn_ballot_w64(idle);
-            nidle = static_cast<uint32_t>(__popcll(im));
-          } while (nidle < level);
-        }
-        __syncthreads();  // the next round rewrites subq and qhead
-        jb = je;
-      }
+      constexpr int S = D == NqDrain::split1 ? 1 : 2;
+      d = nq_drain_split<G1, S>(tile, lds.drain, njobs, msk, N, g, refill);
     }
-    // 32-bit per-lane counters: a block's whole queue is at most 1024 jobs of
-    // <= 109,600 nodes each, below 2^32, whichever lane walks what
-    extra += st.tree;
-    sols += st.sol;
+    extra += d.nodes;
+    extra += d.tree;
+    sols += d.sol;
   }
   uint32_t totC;
   const uint32_t pre = block_excl_scan(cnt, totC);
@@ -987,7 +1067,7 @@ __global__ void k_nq_x(const DevCtl* ctl, const NQNode* pool, NQNode* childbuf,
 #pragma unroll
     for (int j = 0; j < EMIT_TILE / BLOCK; j++) {
       if (lab[j] == 1) {
-        const NQNode& p = s[lpid[j]];
+        const NQNode& p = tile.s[lpid[j]];
         emit_nq_child(childbuf, slot++, p, p.depth, lk[j]);
       }
     }
@@ -1928,24 +2008,31 @@ int devpool_stride(int lbk) {
 
 void launch_nq_x(const DevCtl* ctl, const NQNode* pool, NQNode* childbuf,
                  uint32_t* blockCounts, unsigned long long* blockSols,
-                 unsigned long long* blockExtra, int N, int g, int finish, int split,
-                 int refill, unsigned long long m, unsigned long long M, hipStream_t s,
-                 int stack, int stack_cap) {
-  refill = refill < 1 ? 1 : refill > 64 ? 64 : refill;  // idle lanes of a 64-lane wave
-  // the kernel's stack writes stay below stack_cap, which stays inside the array
-  stack_cap = stack_cap < 0 || stack_cap > NQ_STACK_CAP ? NQ_STACK_CAP : stack_cap;
+                 unsigned long long* blockExtra, int N, int g, const NqFinishOpts& o,
+                 unsigned long long m, unsigned long long M, hipStream_t s) {
+  // resolved options (nq_finish_opts): refill counts idle lanes of a 64-lane
+  // wave, and the kernel's stack writes stay below stack_cap, inside the array
+  if (o.refill < 1 || o.refill > 64 || o.stack_cap < 0 || o.stack_cap > NQ_STACK_CAP)
+    throw std::logic_error("launch_nq_x: finisher options were not resolved");
   auto go = [&](auto kernel) {
     hipLaunchKernelGGL(kernel, dim3(devpool_grid(M, N, 1)), dim3(BLOCK), 0, s, ctl, pool,
-                       childbuf, blockCounts, blockSols, blockExtra, N, g, finish, refill,
-                       stack_cap, m, M);
+                       childbuf, blockCounts, blockSols, blockExtra, N, g, o.finish, o.refill,
+                       o.stack_cap, m, M);
   };
-  if (stack)
-    g == 1 ? go(k_nq_x<true, NQ_X_STACK>) : go(k_nq_x<false, NQ_X_STACK>);
-  else if (g == 1)
-    split <= 0 ? go(k_nq_x<true, 0>) : split == 1 ? go(k_nq_x<true, 1>) : go(k_nq_x<true, 2>);
-  else
-    split <= 0 ? go(k_nq_x<false, 0>) : split == 1 ? go(k_nq_x<false, 1>)
-                                                   : go(k_nq_x<false, 2>);
+  const NqDrain d = o.stack        ? NqDrain::stack
+                    : o.split <= 0 ? NqDrain::flat
+                    : o.split == 1 ? NqDrain::split1
+                                   : NqDrain::split2;
+  auto pick = [&](auto g1) {
+    constexpr bool G1 = decltype(g1)::value;
+    switch (d) {
+      case NqDrain::flat: return go(k_nq_x<G1, NqDrain::flat>);
+      case NqDrain::split1: return go(k_nq_x<G1, NqDrain::split1>);
+      case NqDrain::split2: return go(k_nq_x<G1, NqDrain::split2>);
+      case NqDrain::stack: return go(k_nq_x<G1, NqDrain::stack>);
+    }
+  };
+  g == 1 ? pick(std::true_type{}) : pick(std::false_type{});
 }
 
 template <int MM>

@@ -144,6 +144,18 @@ struct NqFlat {
       cand = nf;
     }
   }
+
+  // Run the loaded walk to its end: pop / take until no candidate is left at
+  // the job's root. Returns the number of steps.
+  template <bool G1>
+  NQ_HD uint64_t exhaust(uint32_t msk, int g) {
+    uint64_t steps = 0;
+    for (; cand != 0 || stack > 1; steps++) {
+      if (cand == 0) pop(msk);
+      if (cand) take<G1>(msk, g);
+    }
+    return steps;
+  }
 };
 
 // Walk every job `next` hands out, one after the other, in ONE loop: when a
@@ -168,7 +180,7 @@ NQ_HD inline void nq_flat_run(NqFlat<LEVELS>& st, Next&& next, uint32_t msk, int
 
 // ---------------------------------------------------------------------------
 // Sub-jobs: a finisher job split below its root, so that a block's queue holds
-// several short walks per lane instead of one long one (k_nq_x SPLIT >= 1, and
+// several short walks per lane instead of one long one (k_nq_x's split drain, and
 // the CPU entry point nq_finish_block_cpu: the same functions, run in sequence).
 //
 // A job with `rem` rows left is split L = min(S, rem - 1) levels: the split
@@ -294,7 +306,7 @@ NQ_HD inline int nq_job_state(uint64_t pm, uint32_t ref, uint32_t msk, uint32_t&
   return row;
 }
 
-// The drain's refill rule, per wave (k_nq_x SPLIT >= 1 and nq_finish_wave_cpu).
+// The drain's refill rule, per wave (k_nq_x's split drain and nq_finish_wave_cpu).
 // A lane is idle when it has no walk (cand == 0 && stack <= 1). In every
 // iteration the wave counts its idle lanes; it fetches, for all of them at
 // once, when it is not drained and at least `T` of its `lanes` lanes are idle,
@@ -329,7 +341,7 @@ NQ_HD inline bool nq_refill_drains(uint32_t got, uint32_t nidle, uint32_t nsub) 
 inline constexpr int NQ_REFILL_DEFAULT = 24;  // GATS_NQ_REFILL's default
 
 // ---------------------------------------------------------------------------
-// Wave-stack finisher (k_nq_x's stack variant and nq_finish_stack_cpu).
+// Wave-stack finisher (k_nq_x's stack drain and nq_finish_stack_cpu).
 //
 // A lane owns one ROW, not a walk: it takes that row's candidates one per
 // iteration and never backtracks. A child that has children of its own in an
@@ -439,10 +451,7 @@ NQ_HD inline void nq_row_walk(NqRow& r, uint32_t nc, uint32_t n1, uint32_t n2, i
   w.tree = 0;
   w.sol = 0;
   w.template load<true>(nc, n1, n2, N - static_cast<int>(r.h), N, msk, 1);
-  while (w.cand != 0 || w.stack > 1) {
-    if (w.cand == 0) w.pop(msk);
-    if (w.cand) w.template take<G1>(msk, g);
-  }
+  w.template exhaust<G1>(msk, g);
   r.tree += w.tree;
   r.sol += w.sol;
 }

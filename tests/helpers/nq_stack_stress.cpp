@@ -1,5 +1,5 @@
 // Stand-alone sanitizer run of the wave-stack finisher's CPU twin
-// (src/nq_finish_stack_cpu.hpp, i.e. the functions k_nq_x's stack variant runs).
+// (src/nq_finish_cpu.hpp, i.e. the functions k_nq_x's stack drain runs).
 //   g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all \
 //       -Isrc tests/helpers/nq_stack_stress.cpp -o nq_stack_stress
 //   ./nq_stack_stress            # exit status 0, "OK ..." on the last line
@@ -8,32 +8,12 @@
 // that force the fallback included. Every run must count what one flat walk
 // per job counts and keep its stacks within the capacity; the sanitizers watch
 // the stack indexing, the shifts and the entry codec.
-#include <algorithm>
-#include <array>
 #include <cstdio>
-#include <cstdlib>
-#include <random>
-#include <vector>
 
-#include "nq_finish_stack_cpu.hpp"
+#include "nq_finish_cpu.hpp"
+#include "nq_stress_jobs.hpp"
 
 using namespace gats;
-
-static std::array<uint32_t, 4> random_job(std::mt19937& rng, int N, int rows) {
-  const int row = N - rows;
-  std::vector<int> colsv(N);
-  for (int i = 0; i < N; i++) colsv[i] = i;
-  std::shuffle(colsv.begin(), colsv.end(), rng);
-  uint32_t cols = 0, d1 = 0, d2 = 0;
-  for (int qr = 0; qr < row; qr++) {
-    const int qc = colsv[qr];
-    cols |= 1u << qc;
-    const int a = qc + (row - qr), b = qc - (row - qr);
-    if (a >= 0 && a < N) d1 |= 1u << a;
-    if (b >= 0 && b < N) d2 |= 1u << b;
-  }
-  return {cols, d1, d2, static_cast<uint32_t>(row)};
-}
 
 int main() {
   std::mt19937 rng(20240117);
@@ -46,18 +26,7 @@ int main() {
     std::vector<std::array<uint32_t, 4>> jobs;
     for (int i = 0; i < njobs; i++) jobs.push_back(random_job(rng, N, pick(1, N < 8 ? N : 8)));
     uint64_t tree = 0, sol = 0;
-    const uint32_t msk = (1u << N) - 1u;
-    for (const auto& j : jobs) {
-      NqFlat<NQ_FLAT_LEVELS_DEV> w;
-      w.tree = w.sol = 0;
-      w.load<true>(j[0], j[1], j[2], static_cast<int>(j[3]), N, msk, 1);
-      while (w.cand != 0 || w.stack > 1) {
-        if (w.cand == 0) w.pop(msk);
-        if (w.cand) w.take<true>(msk, 1);
-      }
-      tree += w.tree;
-      sol += w.sol;
-    }
+    for (const auto& j : jobs) nq_job_walk(j, N, tree, sol);
     const int lanes = round % 3 == 0 ? pick(1, 64) : 64;
     const int waves = pick(1, 4), T = pick(1, 64), g = pick(1, 2);
     const int cap = caps[rng() % (sizeof(caps) / sizeof(caps[0]))];

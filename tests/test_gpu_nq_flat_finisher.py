@@ -18,25 +18,9 @@ import pytest
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "helpers"))
 import devpool_step_oracle as orc  # noqa: E402
+from nq_finish_cases import TILE, leaf, one_job_node, root, run_nq  # noqa: E402
 
 pytestmark = pytest.mark.gpu
-
-TILE = 1024  # child slots per block
-
-_oracle_cache = {}
-
-
-def run_nq(gpu, pool, N, g=1, finish=8, m=1, M=None, what=""):
-    key = (pool, N, finish, m, M)  # the oracle's counts do not depend on g
-    if key not in _oracle_cache:
-        _oracle_cache[key] = orc.nq_step(gpu, pool, N, 1, finish, m, M)
-    exp = _oracle_cache[key]
-    a = gpu.nq_devpool_step(pool, N, g, finish, m, M, None, "auto")
-    b = gpu.nq_devpool_step(pool, N, g, finish, m, M, None, "auto")
-    what = ("nq", what, "N", N, "n", len(pool) // 24, "g", g, "finish", finish, "m", m, "M", M)
-    assert a == b, (what, "two runs differ")
-    orc.check_step(exp, a[0], a[1], what)
-    return exp, a
 
 
 def classify(core, pool, N, finish):
@@ -65,24 +49,6 @@ def classify(core, pool, N, finish):
 
 def njobs(blk):
     return sum(v for key, v in blk.items() if isinstance(key, tuple))
-
-
-def one_job_node(core, rng, N):
-    """A depth N-2 node (two candidate children, one row below them) of which
-    exactly one child is safe."""
-    while True:
-        node = orc.random_nq_nodes(rng, 1, N, N - 2, N - 2)
-        lab = core.nq_cpu_labels(N, 1, node)
-        if sum(lab[k] == 1 for k in range(N - 2, N)) == 1:
-            return node
-
-
-def root(N):
-    return orc.nq_node(0, list(range(N)))
-
-
-def leaf(N):
-    return orc.nq_node(N, list(range(N)))
 
 
 @pytest.mark.parametrize("N", [5, 9, 13, 20])

@@ -11,6 +11,7 @@ kernel's run freely, so its heights can differ, but a `stack_cap` of 0 forces
 the fallback for every push and the capacity bounds every height whatever the
 order. No case needs a fault or a hang to fail: wrong counts fail the compare.
 """
+import functools
 import os
 import sys
 from collections import Counter
@@ -19,67 +20,12 @@ import pytest
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "helpers"))
 import devpool_step_oracle as orc  # noqa: E402
+import nq_finish_cases  # noqa: E402
+from nq_finish_cases import block_jobs, leaf, one_job_node, root  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-TILE = 1024  # child slots per block
-
-_oracle_cache = {}
-
-
-def block_jobs(core, pool, N, finish):
-    """Per block, the finisher jobs in queue (= slot) order, as the states
-    (cols, d1, d2, row) below the safe child."""
-    n = len(pool) // 24
-    labels = core.nq_cpu_labels(N, 1, pool)
-    msk = (1 << N) - 1
-    blocks = [[] for _ in range((n * N + TILE - 1) // TILE)]
-    for t in range(n * N):
-        pid, k = divmod(t, N)
-        node = pool[pid * 24:(pid + 1) * 24]
-        depth = node[0]
-        if depth >= N or k < depth or labels[t] != 1 or not 0 < N - depth - 1 <= finish:
-            continue
-        cols = d1 = d2 = 0
-        for col in list(node[1:1 + depth]) + [node[1 + k]]:
-            cols |= 1 << col
-            d1 = ((d1 | 1 << col) << 1) & msk
-            d2 = (d2 | 1 << col) >> 1
-        blocks[t // TILE].append((cols, d1, d2, depth + 1))
-    return blocks
-
-
-def one_job_node(core, rng, N):
-    """A depth N-2 node of which exactly one child is safe: one job with one
-    row left."""
-    while True:
-        node = orc.random_nq_nodes(rng, 1, N, N - 2, N - 2)
-        lab = core.nq_cpu_labels(N, 1, node)
-        if sum(lab[k] == 1 for k in range(N - 2, N)) == 1:
-            return node
-
-
-def root(N):
-    return orc.nq_node(0, list(range(N)))
-
-
-def leaf(N):
-    return orc.nq_node(N, list(range(N)))
-
-
-def run_nq(gpu, pool, N, g=1, finish=8, m=1, M=None, refill=-1, stack_cap=-1, what=""):
-    key = (pool, N, finish, m, M)  # the oracle's counts depend on neither g nor the finisher
-    if key not in _oracle_cache:
-        _oracle_cache[key] = orc.nq_step(gpu, pool, N, 1, finish, m, M)
-    exp = _oracle_cache[key]
-    args = (pool, N, g, finish, m, M, None, "auto", 0, -1, refill, 1, stack_cap)
-    a = gpu.nq_devpool_step(*args)
-    b = gpu.nq_devpool_step(*args)
-    what = ("nq stack", what, "N", N, "n", len(pool) // 24, "g", g, "finish", finish,
-            "refill", refill, "stack_cap", stack_cap)
-    assert a == b, (what, "two runs differ")
-    orc.check_step(exp, a[0], a[1], what)
-    return exp, a
+run_nq = functools.partial(nq_finish_cases.run_nq, stack=1)
 
 
 def shape(core, pool, N, finish=8, refill=None, cap=None):

@@ -14,59 +14,14 @@ The packed parent masks (nq_pmask_pack / nq_pmask_unpack) and the job
 reference that carries the child's column (nq_job_ref / nq_job_state) are
 checked against masks stepped in Python and nq_finish_count_cpu, N = 4..20.
 """
+import os
 import random
+import sys
 
 import pytest
 
-
-def free_mask(cols, d1, d2, N):
-    return ~(cols | d1 | d2) & ((1 << N) - 1)
-
-
-def bits(f):
-    while f:
-        b = f & -f
-        f ^= b
-        yield b
-
-
-def step(cols, d1, d2, b, N):
-    msk = (1 << N) - 1
-    return cols | b, ((d1 | b) << 1) & msk, (d2 | b) >> 1
-
-
-def fanout(job, N, split):
-    """Sub-jobs of one job, from the masks alone."""
-    cols, d1, d2, row = job
-    lv = max(0, min(split, N - row - 1))
-    if lv == 0:
-        return 1
-    f0 = free_mask(cols, d1, d2, N)
-    if lv == 1:
-        return bin(f0).count("1")
-    return sum(bin(free_mask(*step(cols, d1, d2, b, N), N)).count("1") for b in bits(f0))
-
-
-def random_job(rng, N, rows):
-    """A state with `rows` empty rows: distinct random columns for the rows
-    above (they may attack each other diagonally: the walk is a function of the
-    masks)."""
-    row = N - rows
-    cols = d1 = d2 = 0
-    for qr, qc in enumerate(rng.sample(range(N), row)):
-        cols |= 1 << qc
-        a, b = qc + (row - qr), qc - (row - qr)
-        if 0 <= a < N:
-            d1 |= 1 << a
-        if 0 <= b < N:
-            d2 |= 1 << b
-    return cols, d1, d2, row
-
-
-def jobs_n13():
-    rng = random.Random(1300)
-    return [random_job(rng, 13, rows) for rows in range(1, 9) for _ in range(12)]
-
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "helpers"))
+from nq_finish_cases import fanout, free_mask, jobs_n13, random_job, step  # noqa: E402
 
 SPLITS = (1, 2)
 GS = (1, 2)

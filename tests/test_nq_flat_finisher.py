@@ -4,7 +4,13 @@ nq_finish_count_cpu runs the very loop k_nq_x's phase C runs (src/nq_finish.hpp)
 over one job; it must count what a plain recursive placement counts: every
 safe node below the job's state (tree) and every full board (sol).
 """
+import os
+import sys
+
 import pytest
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "helpers"))
+from nq_finish_cases import masks  # noqa: E402
 
 SOLUTIONS = {4: 2, 5: 10, 6: 4, 7: 40, 8: 92, 9: 352, 10: 724, 11: 2680}
 
@@ -48,20 +54,6 @@ def ref_walk(N):
 def ref_count(N, row, queens):
     assert len(queens) == row
     return ref_walk(N)[tuple(queens)]
-
-
-def masks(N, row, queens):
-    """(cols, d1, d2) as the kernel steps them: the squares of `row` attacked
-    by column, by the diagonal moving right and by the one moving left."""
-    cols = d1 = d2 = 0
-    for qr, qc in queens:
-        cols |= 1 << qc
-        a, b = qc + (row - qr), qc - (row - qr)
-        if 0 <= a < N:
-            d1 |= 1 << a
-        if 0 <= b < N:
-            d2 |= 1 << b
-    return cols, d1, d2
 
 
 def boards_at(N, depth):

@@ -1,7 +1,7 @@
 """The split finisher's queue logic on the CPU.
 
 nq_finish_block_cpu pushes a list of finisher jobs through the functions
-k_nq_x runs with SPLIT >= 1 (src/nq_finish.hpp): the split pass that counts and
+k_nq_x's split drain runs (src/nq_finish.hpp): the split pass that counts and
 ranks the sub-jobs, the rounds cut, the entry codec, the sub-job load and the
 flat loop, one after the other. Whatever the split depth and the queue
 capacity, it must count what nq_finish_count_cpu counts over the same jobs;
@@ -11,39 +11,16 @@ A qcap below one job's fan-out is REJECTED (ValueError naming the job): the
 kernel's QCAP is at least the largest fan-out (56) by a static_assert, so the
 case cannot arise there.
 """
+import os
 import random
+import sys
 
 import pytest
 
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "helpers"))
+from nq_finish_cases import fanout, free_mask, jobs_n13, random_job  # noqa: E402
+
 SPLITS = (0, 1, 2)
-
-
-def free_mask(cols, d1, d2, N):
-    return ~(cols | d1 | d2) & ((1 << N) - 1)
-
-
-def bits(f):
-    while f:
-        b = f & -f
-        f ^= b
-        yield b
-
-
-def step(cols, d1, d2, b, N):
-    msk = (1 << N) - 1
-    return cols | b, ((d1 | b) << 1) & msk, (d2 | b) >> 1
-
-
-def fanout(job, N, split):
-    """Sub-jobs of one job, from the masks alone."""
-    cols, d1, d2, row = job
-    lv = max(0, min(split, N - row - 1))
-    if lv == 0:
-        return 1
-    f0 = free_mask(cols, d1, d2, N)
-    if lv == 1:
-        return bin(f0).count("1")
-    return sum(bin(free_mask(*step(cols, d1, d2, b, N), N)).count("1") for b in bits(f0))
 
 
 def rounds_of(counts, qcap):
@@ -55,22 +32,6 @@ def rounds_of(counts, qcap):
             fill = 0
         fill += n
     return rounds
-
-
-def random_job(rng, N, rows):
-    """A state with `rows` empty rows: distinct random columns for the rows
-    above (they may attack each other diagonally: the walk is a function of the
-    masks)."""
-    row = N - rows
-    cols = d1 = d2 = 0
-    for qr, qc in enumerate(rng.sample(range(N), row)):
-        cols |= 1 << qc
-        a, b = qc + (row - qr), qc - (row - qr)
-        if 0 <= a < N:
-            d1 |= 1 << a
-        if 0 <= b < N:
-            d2 |= 1 << b
-    return cols, d1, d2, row
 
 
 _want = {}
@@ -95,11 +56,6 @@ def check(core, jobs, N, split, qcap, g=1):
     assert got[2] == sum(counts), (N, split, qcap, g)
     assert got[3] == rounds_of(counts, qcap), (N, split, qcap, g)
     return counts
-
-
-def jobs_n13():
-    rng = random.Random(1300)
-    return [random_job(rng, 13, rows) for rows in range(1, 9) for _ in range(12)]
 
 
 @pytest.mark.parametrize("g", [1, 2])

@@ -13,26 +13,14 @@ makes every push fall back, cap = 64 lets a wave push onto an empty stack only
 (one iteration's pushes, then it falls back until the stack is empty again),
 and cap = 65..130 mixes the two further. The peak height is at most cap, always.
 """
+import os
 import random
+import sys
 
 import pytest
 
-
-def random_job(rng, N, rows):
-    """A state with `rows` empty rows: distinct random columns for the rows
-    above (they may attack each other diagonally: the walk is a function of the
-    masks)."""
-    row = N - rows
-    cols = d1 = d2 = 0
-    for qr, qc in enumerate(rng.sample(range(N), row)):
-        cols |= 1 << qc
-        a, b = qc + (row - qr), qc - (row - qr)
-        if 0 <= a < N:
-            d1 |= 1 << a
-        if 0 <= b < N:
-            d2 |= 1 << b
-    return cols, d1, d2, row
-
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "helpers"))
+from nq_finish_cases import jobs_n13, random_job  # noqa: E402
 
 _count = {}
 
@@ -56,11 +44,6 @@ def check(core, jobs, N, g=1, refill=24, waves=4, lanes=64, cap=None):
     assert len(iters) == len(peak) == waves
     assert max(peak) <= cap, what
     return iters, peak, fb
-
-
-def jobs_n13():
-    rng = random.Random(1300)
-    return [random_job(rng, 13, rows) for rows in range(1, 9) for _ in range(12)]
 
 
 def tall_jobs(n=200, N=13, seed=77):
